@@ -7,6 +7,12 @@ resident in HBM).  `value` = uncompressed bytes processed by ALL ranks / wall ti
 slice in both directions, benches/density.rs:29,48).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--size BYTES] [--chunk BYTES] [--algo chameleon|cheetah|lion]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, checks one round trip on the device, warms up, times the K steps and prints the result line.  `--full` adds
+everything else: the oracle comparisons of the GPU's chunk streams, the other container forms, the size sweep, the CPU baselines and
+host-API rates, the hostile data kinds and BASELINE's other configurations (`--no-cpu` / `--no-sweep` / `--no-extra` leave parts of it
+out).  `--dump-outputs DIR` writes what the last timed step computed (rank 0's) as float .npy files: see dump_outputs().
 
 N > 1: one rank per GPU over RCCL.  Launched by the driver through torch.distributed.run, or — when WORLD_SIZE is not set —
 by this script itself, which re-executes under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N`.  The path
@@ -433,6 +439,34 @@ def strict_stream_leg(host, x, steps=5, label=None):
             "oracle_prefix_compared_bytes": int(k), "decode_is_the_input": True,
             "roofline": {"encode": roofline_entry("strict stream encode (all passes)", n + E, e_ms), "decode": roofline_entry("strict stream decode (all passes)", n + E, d_ms)}}
 
+DUMP_SAMPLE = 1 << 22          # bytes kept of each sampled output: 16 MB as float32
+
+
+def dump_outputs(out_dir, container, cont, container_len, back):
+    """--dump-outputs: what the last timed step left for its caller, as `out_dir`/<name>.npy (about 32 MB in all):
+      decoded.npy      float32  the decoded buffer (equal to the input): whole up to DUMP_SAMPLE bytes, else DUMP_SAMPLE bytes at seeded positions
+      encoded.npy      float32  the container's chunk streams, concatenated in chunk order, sampled the same way.  Where the timed form keeps a
+                                stream (slots, pages) is placement, not content: the paged form takes its pages in the order the work-groups finish
+      chunk_sizes.npy  float64  the length of every chunk's stream
+      chunk_sums.npy   float64  the sum of the bytes of every chunk's stream (the whole container, not a sample)
+    The inputs are seeded and so are the positions: the same arguments give the same arrays from one run and one build to the next."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+
+    def positions(n, seed):
+        return None if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(seed).integers(0, n, size=DUMP_SAMPLE))
+
+    at = positions(back.numel(), 0xDEC0DE)
+    dec = back if at is None else back[torch.from_numpy(at).to(back.device)]
+    np.save(os.path.join(out_dir, "decoded.npy"), dec.cpu().numpy().astype(np.float32))
+    _, streams = container.chunk_payloads(cont[:container_len].cpu().numpy())
+    np.save(os.path.join(out_dir, "chunk_sizes.npy"), np.array([len(p) for p in streams], dtype=np.float64))
+    np.save(os.path.join(out_dir, "chunk_sums.npy"), np.array([int(np.frombuffer(p, dtype=np.uint8).sum(dtype=np.uint64)) for p in streams], dtype=np.float64))
+    flat = np.frombuffer(b"".join(streams), dtype=np.uint8)
+    at = positions(flat.size, 0xE4C0DE)
+    np.save(os.path.join(out_dir, "encoded.npy"), (flat if at is None else flat[at]).astype(np.float32))
+
+
 def self_launch(args):
     """--gpus N without a torchrun environment: start the N ranks ourselves (one node, 127.0.0.1 rendezvous)."""
     import socket
@@ -489,9 +523,14 @@ def main():
     ap.add_argument("--chunk", type=int, default=0, help="container chunk size; 0 = the library's automatic choice (density_hip_auto_chunk: 4 MiB at 1 GiB)")
     ap.add_argument("--cpu-sample", type=int, default=256 << 20)
     ap.add_argument("--host-sample", type=int, default=64 << 20, help="bytes for the PCIe-inclusive host-API rates")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline and the host-API legs")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the size sweep (profiling runs: only the headline workload's launches)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the other_configs legs (configs 3/4, strict stream): only the headline workload")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: oracle comparisons, the other container forms, the size sweep, CPU baselines, host-API rates, "
+                         "data kinds and the other configurations (a plain run measures the headline workload only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's) to DIR/<name>.npy as float32 / float64")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline and the host-API legs")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: skip the size sweep (profiling runs: only the headline workload's launches)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the other container forms and the other_configs legs (configs 3/4, strict stream)")
     ap.add_argument("--no-gpu", action="store_true", help="dry mode: launcher + distributed bookkeeping on CPU/gloo (tests)")
     ap.add_argument("--packed", action="store_true", help="time the packed container (encode + stitch pass + decode) instead of the paged one")
     ap.add_argument("--slotted", action="store_true", help="time the slotted container (rounds 3-4's `value`: no stitch, not wire-ready) instead of the paged one")
@@ -516,7 +555,6 @@ def main():
     import torch.distributed as dist
     import datagen
     from density_amd import container
-    from oracle import pyoracle
 
     # One rank per GPU over RCCL whenever a launcher set the rendezvous up — including a world of ONE (WORLD_SIZE=1 in the environment:
     # the whole process-group branch — init, the size all-gather, the optional concat — then runs on a single GPU, which is how
@@ -558,15 +596,19 @@ def main():
     form = "packed" if args.packed else ("slotted" if args.slotted else "paged")
     enc_dev = {"packed": container.encode_device, "slotted": container.encode_device_slotted, "paged": container.encode_device_paged}[form]
 
-    # correctness before any timing: decode(encode(x)) == x, and chunk streams equal to the oracle's (all of the CPU sample's chunks are
-    # compared in cpu_baseline; here a spread of chunks so that --no-cpu runs are checked too)
+    # correctness before any timing: decode(encode(x)) == x on the device; with --full also chunk streams equal to the oracle's (all of the CPU
+    # sample's chunks are compared in cpu_baseline; here a spread of chunks so that --no-cpu runs are checked too)
     hdr_p = container.encode_device(algo, x.data_ptr(), n, cont.data_ptr(), cap, chunk, stream=s, workspace=(ws.data_ptr(), ws_size))
     got = container.decode_device(cont.data_ptr(), hdr_p.container_len, back.data_ptr(), n, header=hdr_p, stream=s, workspace=(ws.data_ptr(), ws_size))
     assert got == n and torch.equal(back, x), "round trip mismatch"
-    raw = cont[:hdr_p.container_len].cpu().numpy()
-    _, payloads = container.chunk_payloads(raw)
-    for i in sorted(set([0, hdr_p.n_chunks // 3, hdr_p.n_chunks - 1])):
-        assert payloads[i] == pyoracle.encode(algo, host[i * chunk:(i + 1) * chunk]), f"chunk {i} differs from the oracle"
+    payloads = None
+    if args.full:
+        from oracle import pyoracle
+        raw = cont[:hdr_p.container_len].cpu().numpy()
+        _, payloads = container.chunk_payloads(raw)
+        for i in sorted(set([0, hdr_p.n_chunks // 3, hdr_p.n_chunks - 1])):
+            assert payloads[i] == pyoracle.encode(algo, host[i * chunk:(i + 1) * chunk]), f"chunk {i} differs from the oracle"
+        del raw
     E = int(hdr_p.container_len)                       # the PACKED container: the algorithmic E of the roofline (the fewest bytes the streams + tables can take)
     hdr, Ec = hdr_p, E
     packed_ref = cont[:E].clone()
@@ -580,17 +622,17 @@ def main():
             form = "slotted"                            # shapes the paged form is not for come out slotted (the header says so)
         got = container.decode_device(cont.data_ptr(), Ec, back.data_ptr(), n, header=hdr, stream=s, workspace=(ws.data_ptr(), ws_size))
         assert got == n and torch.equal(back, x), f"round trip mismatch ({form} container)"
-        _, payloads_f = container.chunk_payloads(cont[:Ec].cpu().numpy())
-        assert payloads_f == payloads, f"the {form} container's chunk streams differ from the packed container's"
-        del payloads_f
-        if form == "slotted":
-            repacked = torch.empty(cap, dtype=torch.uint8, device="cuda")
-            hr = container.pack_device(cont.data_ptr(), Ec, repacked.data_ptr(), cap, header=hdr, stream=s, workspace=(ws.data_ptr(), ws_size))
-            assert hr.container_len == E and torch.equal(repacked[:E], packed_ref), "pack(slotted) differs from the packed container"
-            del repacked
+        if args.full:
+            _, payloads_f = container.chunk_payloads(cont[:Ec].cpu().numpy())
+            assert payloads_f == payloads, f"the {form} container's chunk streams differ from the packed container's"
+            del payloads_f
+            if form == "slotted":
+                repacked = torch.empty(cap, dtype=torch.uint8, device="cuda")
+                hr = container.pack_device(cont.data_ptr(), Ec, repacked.data_ptr(), cap, header=hdr, stream=s, workspace=(ws.data_ptr(), ws_size))
+                assert hr.container_len == E and torch.equal(repacked[:E], packed_ref), "pack(slotted) differs from the packed container"
+                del repacked
     # the bytes `value` is about: what has to leave the device for the container to be decodable elsewhere
     wire_bytes = Ec if form in ("paged", "packed") else E
-    del raw
 
     def step():
         enc_dev(algo, x.data_ptr(), n, cont.data_ptr(), cap, chunk, stream=s, workspace=(ws.data_ptr(), ws_size), want_header=False)
@@ -622,6 +664,8 @@ def main():
         per_rank_ms = [float(v.item()) / args.steps * 1e3 for v in all_t]
         dt = max(float(v.item()) for v in all_t)
     assert torch.equal(back, x), "round trip mismatch after timed steps"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, container, cont, Ec, back)         # (before anything below reuses `cont` and `back`)
     # the other container forms through the same round trip, a few steps each, for the record (never `value`)
     def side_form(fname):
         fenc = {"packed": container.encode_device, "slotted": container.encode_device_slotted, "paged": container.encode_device_paged}[fname]
@@ -651,7 +695,7 @@ def main():
                 "whole_path_hbm_frac": round(2.0 * (n + E) / dtp / 1e9 / HBM_PEAK_GBS, 5), "container_bytes": flen,
                 "wire_ready": fname != "slotted", "note": notes[fname]}
     side = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         for fname in ("packed", "slotted", "paged"):
             if fname != form and not (fname == "paged" and form == "slotted" and not args.slotted):
                 side[fname] = side_form(fname)
@@ -789,12 +833,12 @@ def main():
                           "multi_container": {"format": "DHCM: the ranks' timed blobs as they stand behind a 32-byte header and a 24-byte row per rank", "bytes": int(mlen),
                                               "ranks": len(mrows), "gather_ms": round(multi_gather_ms, 3)}},
         }
-        if n_gpus == 1 and not args.no_sweep:
+        if args.full and n_gpus == 1 and not args.no_sweep:
             result["size_sweep"] = size_sweep(container, algo, x, [10_000_000, 100_000_000, n])
-        if not args.no_cpu and n_gpus == 1:                                              # (rank 0 at N = 1 only: at N > 1 the other ranks would sit in the final barrier meanwhile)
+        if args.full and not args.no_cpu and n_gpus == 1:                                # (rank 0 at N = 1 only: at N > 1 the other ranks would sit in the final barrier meanwhile)
             result["cpu_baseline"] = cpu_baseline(host, chunk, args.cpu_sample, algo, gpu_payloads=payloads)
             result["host_api"] = host_api_rates(algo, host, chunk, args.host_sample)
-        if n_gpus == 1 and not args.no_extra and algo == "chameleon" and args.data == "rep-text":
+        if args.full and n_gpus == 1 and not args.no_extra and algo == "chameleon" and args.data == "rep-text":
             # SURVEY.md 8d's hostile inputs at their stated size through the same device container path (never `value`): all-zero (every quad hits:
             # chameleon.rs:88-100), xorshift-random (the blow-up protection turns most blocks into raw copies: protection_state.rs:19-47) and a
             # patchwork of text / random / zeros / low-entropy runs that drives the FSM in and out — with per-direction roofline entries

@@ -35,7 +35,7 @@ timeout 120 ./probes/vmem_width > $R/$OUT/vmem_width.txt 2>/dev/null
 # (the cycle accounting is compiled into the debug build only: tools/gpu_phase_prof.py loads it)
 : > $R/$OUT/phase_profile.txt
 for k in text random mixed; do DENSITY_HIP_PROF=1 timeout 300 python tools/gpu_phase_prof.py $k 2>&1 | grep -v amdgpu.ids >> $R/$OUT/phase_profile.txt; done
-timeout 600 python bench.py --steps 10 --warmup 3 --no-extra > $R/$OUT/bench.json 2>/dev/null
+timeout 600 python bench.py --full --steps 10 --warmup 3 --no-extra > $R/$OUT/bench.json 2>/dev/null
 # the packed container (with the stitch pass) and Cheetah at its automatic chunk, kernel by kernel
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats_packed -- $B --packed --steps 5 --warmup 1 > $R/$OUT/bench_stats_packed.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats_slotted -- $B --slotted --steps 5 --warmup 1 > $R/$OUT/bench_stats_slotted.log 2>&1

@@ -44,3 +44,36 @@ def test_direction_traffic_is_only_quoted_for_its_workload():
         assert set(got) == {"encode", "decode"} and all(v[0] > 100_000_000 for v in got.values())
     else:
         assert got == {}                                                               # counters of another kernel generation are not this library's
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs without a GPU: a container of oracle streams and its decoded buffer, as CPU tensors, go out as float arrays that hold the
+    decoded bytes and the chunk streams in chunk order; a larger output is sampled, at the same positions every time."""
+    import torch
+    from density_amd import container
+    from test_parallel_gloo import cpu_container
+    data, chunk = datagen.mixed(300_000, seed=11), 65536
+    cont = torch.frombuffer(bytearray(cpu_container(data, chunk)), dtype=torch.uint8)
+    clen = int(container.parse_header(bytes(cont[:32].numpy())).container_len)
+    streams = [pyoracle.encode("chameleon", data[i:i + chunk]) for i in range(0, data.size, chunk)]
+
+    def dump(name):
+        bench.dump_outputs(str(tmp_path / name), container, cont, clen, torch.from_numpy(data.copy()))
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["chunk_sizes.npy", "chunk_sums.npy", "decoded.npy", "encoded.npy"]
+        assert sum(os.path.getsize(tmp_path / name / f) for f in files) <= 64 << 20
+        got = {f[:-4]: np.load(tmp_path / name / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        return got
+
+    whole = dump("whole")
+    assert np.array_equal(whole["decoded"], data.astype(np.float32))
+    assert np.array_equal(whole["encoded"], np.frombuffer(b"".join(streams), dtype=np.uint8).astype(np.float32))
+    assert whole["chunk_sizes"].tolist() == [len(s) for s in streams]
+    assert whole["chunk_sums"].tolist() == [sum(s) for s in streams]
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 4096)
+    a, b = dump("a"), dump("b")
+    assert a["decoded"].size == a["encoded"].size == 4096
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert np.array_equal(a["chunk_sums"], whole["chunk_sums"])
+    assert set(a["decoded"].tolist()) <= set(whole["decoded"].tolist())

@@ -10,7 +10,7 @@ echo "elapsed $(( $(date +%s) - $(cat $T/t0) )) s"
 bash probes/profile_round.sh gpurun_out/prof6 > $T/profile_round.log 2>&1; echo "profile rc=$?"; tail -3 $T/profile_round.log
 bash probes/profile_directions.sh gpurun_out/prof6d > $T/profile_directions.log 2>&1; echo "directions rc=$?"
 echo "elapsed $(( $(date +%s) - $(cat $T/t0) )) s"
-timeout 900 python bench.py --steps 20 --warmup 5 > $T/bench_full.json 2> $T/bench_full.err; echo "bench rc=$?"; head -c 300 $T/bench_full.json; echo
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $T/bench_full.json 2> $T/bench_full.err; echo "bench rc=$?"; head -c 300 $T/bench_full.json; echo
 timeout 400 python benches/density.py > $T/benches_density.txt 2>&1; echo "harness rc=$?"; tail -24 $T/benches_density.txt
 timeout 200 python tools/gpu_forms.py 10 2>&1 | grep -v amdgpu.ids > $T/forms.txt; tail -6 $T/forms.txt
 for f in encode streams passes tail paged; do timeout 200 python tools/gpu_fuzz_$f.py > $T/fuzz_$f.log 2>&1; echo "fuzz $f rc=$?"; tail -2 $T/fuzz_$f.log; done
