@@ -24,11 +24,39 @@ class DecodeError(Exception):
     """errors/decode_error.rs"""
 
 
+def _c_contiguous(ai):
+    """True if an __array_interface__ describes one C-ordered run of bytes (strides None, or the C strides of its shape)."""
+    strides = ai.get("strides")
+    if strides is None:
+        return True
+    shape = ai["shape"]
+    if 0 in shape:
+        return True
+    step = int(ai["typestr"][2:])
+    for dim, stride in zip(reversed(shape), reversed(strides)):
+        if dim != 1 and stride != step:
+            return False
+        step *= dim
+    return True
+
+
+def _contiguous_view(buf):
+    """buffer -> a flat byte memoryview of it; TypeError for a strided / reversed / Fortran-ordered view: the library is handed one address and a
+    length, which describe only a C-contiguous buffer (the bytes of anything else are not where those two say)."""
+    mv = memoryview(buf)
+    if not mv.c_contiguous:
+        raise TypeError("buffer is not C-contiguous (strided, reversed or Fortran-ordered view): pass a contiguous copy")
+    return mv.cast("B")
+
+
 def _ro(buf):
     """read-only buffer -> (address, nbytes, keepalive)"""
     if hasattr(buf, "__array_interface__"):
-        return buf.__array_interface__["data"][0], buf.nbytes, buf
-    mv = memoryview(buf).cast("B")
+        ai = buf.__array_interface__
+        if not _c_contiguous(ai):
+            raise TypeError("input buffer is not C-contiguous (strided, reversed or Fortran-ordered view): pass a contiguous copy")
+        return ai["data"][0], buf.nbytes, buf
+    mv = _contiguous_view(buf)
     n = mv.nbytes
     if n == 0:
         return 0, 0, mv
@@ -41,10 +69,13 @@ def _ro(buf):
 
 def _rw(buf):
     if hasattr(buf, "__array_interface__"):
-        if buf.__array_interface__["data"][1]:
+        ai = buf.__array_interface__
+        if ai["data"][1]:
             raise TypeError("output buffer is read-only")
-        return buf.__array_interface__["data"][0], buf.nbytes, buf
-    mv = memoryview(buf).cast("B")
+        if not _c_contiguous(ai):
+            raise TypeError("output buffer is not C-contiguous (strided, reversed or Fortran-ordered view): pass a contiguous buffer")
+        return ai["data"][0], buf.nbytes, buf
+    mv = _contiguous_view(buf)
     if mv.readonly:
         raise TypeError("output buffer is read-only")
     n = mv.nbytes

@@ -371,7 +371,7 @@ int run_stream_decode(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, uin
     // scratch cannot be had (the passes are an optimisation, not a requirement).
     uint8_t* d_pass = nullptr;
     const size_t pass_cap = algo == DENSITY_HIP_CHEETAH ? std::min<size_t>(cap, (n / 8 + 2) * 128) : cap;
-    if (e == hipSuccess && n >= 16384 && decode_pass_eligible(algo, d_out, 1, pass_cap, pass_cap)) {
+    if (e == hipSuccess && n >= 16384 && decode_pass_eligible(algo, d_in, d_out, 1, pass_cap, pass_cap)) {
         if (c->seg.ensure(decode_pass_scratch_bytes(align_up(pass_cap, 256), 1) + kAlign) == hipSuccess) d_pass = (uint8_t*)c->seg.p;
         else (void)hipGetLastError();                                                // (out of memory for the scratch: the one-wave decoder needs none)
     }

@@ -1418,9 +1418,12 @@ uint64_t decode_pass_scratch_bytes(uint64_t out_stride, uint32_t n_chunks) {
     const uint64_t span = (uint64_t)n_chunks * out_stride;                         // (arrays are indexed chunk * stride + ...)
     return ((span / kRecBytes * 4 + 255) & ~255ull) + ((span + 255) & ~255ull) + ((span / 2 + 255) & ~255ull) + (((uint64_t)n_chunks * sizeof(ChunkInfo) + 255) & ~255ull) + 256;
 }
-bool decode_pass_eligible(int algo, const uint8_t* d_out, uint32_t n_chunks, uint64_t out_stride, uint64_t out_total) {
+bool decode_pass_eligible(int algo, const uint8_t* d_in, const uint8_t* d_out, uint32_t n_chunks, uint64_t out_stride, uint64_t out_total) {
     if (algo != DENSITY_HIP_CHEETAH || g_force_serial_decode || g_force_lane_codec || g_force_wave_codec || g_rotor_unsafe) return false;
     if (n_chunks == 0 || (uintptr_t)d_out % 4 != 0) return false;
+    // the head walk reads a signature as whole 16-bit halves of its window (signature_at: stream positions are even, and so must be the
+    // window's `misalign`); chunk payloads start at 16-byte offsets from d_in, so an odd d_in is the one-wave decoder's
+    if ((uintptr_t)d_in % 2 != 0) return false;
     // one chunk (a stream): the output capacity is the stride; chunks: whole pairs of records
     if (n_chunks > 1 && out_stride % 256 != 0) return false;
     // Where the passes win: from 64 KiB chunks on (measured, 100 MB of prose, decode ms passes / one wave per stream: 64 KiB 3.2 / 3.6,

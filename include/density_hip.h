@@ -78,7 +78,7 @@ enum {
     DENSITY_HIP_ERR_CAPACITY = 2,     /* output or workspace too small */
     DENSITY_HIP_ERR_FORMAT = 3,       /* container header or payload malformed / truncated */
     DENSITY_HIP_ERR_RUNTIME = 4,      /* HIP runtime error, no gfx950 device, failed self-test */
-    DENSITY_HIP_ERR_UNSUPPORTED = 5   /* reserved: algorithm not available on the device path */
+    DENSITY_HIP_ERR_UNSUPPORTED = 5   /* the device path does not take these buffers (a paged container or its output not 4-byte aligned) */
 };
 
 /*
@@ -118,7 +118,8 @@ enum {
  *                             {u32 page, u32 first input block of the chunk coded there, u32 bytes of stream in the page, 0}
  *     (256-byte aligned)  page 0, page 1, ...   (container_len = this base + DENSITY_HIP_PAGE_BYTES * pages in use)
  * Chunk i's reference stream = the first `bytes` of each of its pages, concatenated; the u32 size table holds the sum.  A CPU reader does that and
- * calls the crate; density_hip_decode_device() reads the pages in place. */
+ * calls the crate; density_hip_decode_device() reads the pages in place, and only from a container and into an output that are both
+ * 4-byte aligned (anything else: DENSITY_HIP_ERR_UNSUPPORTED, nothing written; density_hip_decode() on host pointers stages it aligned). */
 #define DENSITY_HIP_FLAG_PAGED 4u
 #define DENSITY_HIP_PAGE_BYTES 65536u
 #define DENSITY_HIP_MAGIC 0x31434844u /* "DHC1" */
@@ -172,8 +173,9 @@ size_t density_hip_decoded_size(const uint8_t* container, size_t container_size)
 size_t density_hip_encode_workspace_size(int algo, size_t input_size, size_t chunk_size);
 size_t density_hip_decode_workspace_size(uint32_t n_chunks);
 /* The same for a container of known shape: includes the scratch of Cheetah's decode passes (a dword and a half per quad: 1.5 x total_len
- * + 1/32; decode_passes.hip).  A workspace of only density_hip_decode_workspace_size() bytes still decodes — Cheetah then on one wave per
- * chunk stream. */
+ * + 1/32; decode_passes.hip).  A workspace of only density_hip_decode_workspace_size() bytes still decodes — Cheetah on one wave per
+ * chunk stream wherever it is smaller than density_hip_decode_workspace_size_for() (that size is set by Lion's tables, and for a few large
+ * chunks it holds the passes' scratch too). */
 size_t density_hip_decode_workspace_size_for(int algo, size_t total_len, size_t chunk_size);
 int density_hip_encode_device(int algo, const void* d_input, size_t input_size, void* d_output, size_t output_capacity,
                               size_t chunk_size, void* d_workspace, size_t workspace_size, void* stream,
