@@ -44,13 +44,13 @@ def build(force=False, verbose=False, debug=False):
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd, cwd=CSRC)
-    # the encoder's hand-issued loads rely on registers the compiler must not have used: checked in the compiled code, every build
+    # what the kernels rely on in the compiled code (the encoder's hand-issued loads, the decoder's waits, Lion's row accesses, no scratch): checked every build
     check = os.path.join(os.path.dirname(HERE), "tools", "check_isa.py")
     if os.path.exists(check):
         r = subprocess.run([sys.executable, check, LIB], capture_output=True, text=True)
         if r.returncode != 0:
             os.remove(LIB)
-            raise RuntimeError("tools/check_isa.py rejected the compiled rotation encoder:\n" + r.stdout + r.stderr)
+            raise RuntimeError("tools/check_isa.py rejected the compiled library:\n" + r.stdout + r.stderr)
     return LIB
 
 

@@ -745,24 +745,21 @@ __global__ __launch_bounds__(64) void cheetah_decode_wave(const uint8_t* __restr
 // =================================================================================================================
 struct Row5 { uint32_t n[5]; };
 __device__ __forceinline__ uint32_t rlane32(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
-__device__ __forceinline__ Row5 row_load(const uint32_t* p) {
-    Row5 r;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) r.n[i] = tbl_load32(p + i);
-    return r;
-}
-// The same as TWO memory instructions (16 + 4 bytes; a row is 4-byte aligned): for a wave that is the only one to touch its tables.  The loads are the caller's to
-// wait for (s_waitcnt vmcnt(0)): the compiler does not count an asm statement's
-__device__ __forceinline__ void row_load_wide(const uint32_t* p, bool on, u32x4& lo, uint32_t& hi) {   // (the lanes that are not `on` keep what they hold)
-    if (on) asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dword %1, %2, off offset:16" : "+v"(lo), "+v"(hi) : "v"(p) : "memory");
-}
-__device__ __forceinline__ void row_store_wide(uint32_t* p, const Row5& r) {
-    const u32x4 lo = {r.n[0], r.n[1], r.n[2], r.n[3]};
-    asm volatile("global_store_dwordx4 %0, %1, off\n\tglobal_store_dword %0, %2, off offset:16" ::"v"(p), "v"(lo), "v"(r.n[4]) : "memory");
+// A row moves as 16 + 4 bytes, TWO memory instructions instead of five (at three streams a CU the Lion kernels are bound by the number of requests the memory
+// system takes, not by their size); a row is 4-byte aligned.  Plain loads and stores the compiler sees: it counts them and waits for a row before its first use.
+// They need no atomics: within a step no lane reads a row that another lane writes (the rows are stored at the step's end), and between one step's stores and the
+// next step's loads every kernel has a statement that clobbers "memory" (tbl_drain(), the LDS ring's reads), which the compiler moves and merges nothing across;
+// one wave's accesses to one address then execute in program order.  The lanes that are not `on` get zeros.  (tools/check_isa.py checks the 16 + 4 bytes.)
+typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ Row5 row_load(const uint32_t* p, bool on) {
+    u32x4 lo = {0u, 0u, 0u, 0u};
+    uint32_t hi = 0u;
+    if (on) { lo = *reinterpret_cast<const u32x4a4*>(p); hi = p[4]; }
+    return Row5{{lo.x, lo.y, lo.z, lo.w, hi}};
 }
 __device__ __forceinline__ void row_store(uint32_t* p, const Row5& r) {
-#pragma unroll
-    for (int i = 0; i < 5; ++i) tbl_store32(p + i, r.n[i]);
+    *reinterpret_cast<u32x4a4*>(p) = u32x4{r.n[0], r.n[1], r.n[2], r.n[3]};
+    p[4] = r.n[4];
 }
 __device__ __forceinline__ Row5 row_from_lane(uint32_t src, const Row5& r) {
     Row5 o;
@@ -856,17 +853,11 @@ __global__ __launch_bounds__(64) void lion_encode_wave(const uint8_t* __restrict
             const uint32_t hprev = bperm(lane ? lane - 1u : 0u, h);
             const uint32_t ps = lane == 0 ? last_hash : hprev;               // lion.rs:213,268
             tbl_drain();
-            // (the row as 16 + 4 bytes, two memory instructions instead of five: at three streams a CU the kernel is bound by the number of requests the memory system
-            // takes.  The pair is asked for BEHIND the row and loads return in order: once the compiler has waited for the pair — it must, before the statement that
-            // names it — the row is in as well)
-            u32x4 row_lo = {0u, 0u, 0u, 0u};
-            uint32_t row_hi = 0u;
-            row_load_wide(t.pred + 5u * ps, act, row_lo, row_hi);
+            Row5 row = row_load(t.pred + 5u * ps, act);
             Pair e0 = act ? tbl_load_pair(t.dict + h) : Pair{0u, 0u};
             const uint32_t qwin_next = window(pos + 4u * nact);                // (on the assumption that the step takes all its blocks)
             const uint64_t peq = same_key_mask64(ps, act), deq = same_key_mask64(h, act);
-            asm volatile("" : "+v"(row_lo), "+v"(row_hi), "+v"(e0.a), "+v"(e0.b));
-            Row5 row = Row5{{row_lo.x, row_lo.y, row_lo.z, row_lo.w, row_hi}};
+            asm volatile("" : "+v"(e0.a), "+v"(e0.b));                       // (the compiler waits for the pair and the row here, not at the head of every round below)
             uint32_t da = e0.a, db = e0.b, pdirty = 0, ddirty = 0;
             const uint64_t pbefore = peq & below, dbefore = deq & below;
             const uint32_t pprev = pbefore ? 63u - (uint32_t)__builtin_clzll(pbefore) : 64u;
@@ -927,7 +918,7 @@ __global__ __launch_bounds__(64) void lion_encode_wave(const uint8_t* __restrict
             const uint32_t myat = myrec == 0 ? 0u : myrec == 1 ? at1 : myrec == 2 ? at2 : at3;
             uint8_t* ip = rec + myat + G::kSig + (incl - ilen);
             if (mine) { if (ilen == 4) st32u(ip, q); else if (ilen == 2) st16u(ip, h); }
-            if (plast && pdirty) row_store_wide(t.pred + 5u * ps, row);
+            if (plast && pdirty) row_store(t.pred + 5u * ps, row);
             if (dlast && ddirty) tbl_store_pair(t.dict + h, Pair{da, db});
             last_hash = rlane32(h, 16u * nlive - 1u);
             guard = g;
@@ -1139,7 +1130,7 @@ __global__ __launch_bounds__(64) void lion_decode_wave(const uint8_t* __restrict
             }
             const uint32_t hprev = bperm(lane ? lane - 1u : 0u, h);
             const uint32_t ps = lane == 0 ? last_hash : hprev;
-            Row5 row = act ? row_load(t.pred + 5u * ps) : Row5{{0u, 0u, 0u, 0u, 0u}};
+            Row5 row = row_load(t.pred + 5u * ps, act);
             const Row5 row_mem = row;                                             // as memory holds it (the repair below starts over from it)
             // ---- dictionary, in dependency order among the lanes that touch it ----
             const uint64_t peq = same_key_mask64(ps, act), deq = same_key_mask64(h, dtouch);
@@ -1213,7 +1204,7 @@ __global__ __launch_bounds__(64) void lion_decode_wave(const uint8_t* __restrict
 #pragma unroll
                         for (int k = 0; k < 5; ++k) r.n[k] = rlane32(row_mem.n[k], i);
                     } else {
-                        r = row_load(t.pred + 5u * ctx);
+                        r = row_load(t.pred + 5u * ctx, true);
                     }
                     const uint32_t f = rlane32(flag, i);
                     uint32_t qi, hi;
@@ -1487,13 +1478,11 @@ __global__ __launch_bounds__(128) void lion_decode_pair(const uint8_t* __restric
                 LP_T(c4);
                 const uint32_t hprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)h, 0x138, 0xf, 0xf, false);   // wave_shr:1
                 const uint32_t ps = lane == 0 ? last_hash : hprev;
-                // the rows: 16 + 4 bytes, two memory instructions (up to here five dwords in five: at three streams a CU the decoder is bound by the number of requests the
-                // memory system takes, not by their size — 2.94 -> 2.68 ms), waited for behind the dictionary rounds, which run under the load
-                u32x4 row_lo = {0u, 0u, 0u, 0u};
-                uint32_t row_hi = 0u;
-                row_load_wide(t.pred + 5u * ps, act, row_lo, row_hi);
+                // the rows: 16 + 4 bytes, two memory instructions (up to here five dwords in five: 2.94 -> 2.68 ms).  The compiler's wait for the pair `e0`, ahead of the
+                // dictionary rounds, is a vmcnt(0): the rows are in before the rounds begin, which do not run under their load
+                Row5 row = row_load(t.pred + 5u * ps, act);
 #ifdef LION_PHASES
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the account's stamp wants the rows in; the shipped kernel lets the dictionary rounds run under their load)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the account's stamp wants the rows in)
 #endif
                 LP_T(c5);
                 const uint64_t peq = same_key_mask64(ps, act);
@@ -1521,8 +1510,6 @@ __global__ __launch_bounds__(128) void lion_decode_pair(const uint8_t* __restric
                     }
                     if (ballot64(!ddone) == 0) break;
                 }
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(row_lo), "+v"(row_hi) : : "memory");
-                Row5 row = Row5{{row_lo.x, row_lo.y, row_lo.z, row_lo.w, row_hi}};
                 const Row5 row_mem = row;                                             // as memory holds it (the repair below starts over from it)
                 LP_T(c6);
                 const uint64_t pbefore = peq & below;
@@ -1608,7 +1595,7 @@ __global__ __launch_bounds__(128) void lion_decode_pair(const uint8_t* __restric
 #pragma unroll
                             for (int k = 0; k < 5; ++k) r.n[k] = rlane32(row_mem.n[k], i);
                         } else {
-                            { u32x4 lo = {0u, 0u, 0u, 0u}; uint32_t hi = 0u; row_load_wide(t.pred + 5u * ctx, true, lo, hi); asm volatile("s_waitcnt vmcnt(0)" : "+v"(lo), "+v"(hi) : : "memory"); r = Row5{{lo.x, lo.y, lo.z, lo.w, hi}}; }
+                            r = row_load(t.pred + 5u * ctx, true);
                         }
                         const uint32_t f = rlane32(flag, i);
                         uint32_t qi, hi;
@@ -1632,7 +1619,7 @@ __global__ __launch_bounds__(128) void lion_decode_pair(const uint8_t* __restric
                     plastf = act && ((peq2 >> lane) >> 1) == 0;
                 }
                 LP_T(c8);
-                if (plastf && pdirty) row_store_wide(t.pred + 5u * psf, row);
+                if (plastf && pdirty) row_store(t.pred + 5u * psf, row);
                 if (dlast && ddirty) tbl_store_pair(t.dict + h, Pair{da, db});
                 last_hash = rlane32(h, nact - 1u);
                 LP_T(c9);

@@ -10,7 +10,8 @@ and checks, for every 8-wave encoder instance, that
     (v_mov_b32 vX, vN), and
   * every run of moves directly follows an s_waitcnt vmcnt(..).
 Also checked: the default decoder's stage B waits with vmcnt(12) and nothing in its round loop drains the memory queue; the
-exchange stage kernels of exchange_stages.hip fit their 256 registers without scratch memory.
+exchange stage kernels of exchange_stages.hip fit their 256 registers without scratch memory; Lion's encoder and pair decoder
+(serial_codec.hip) move a prediction row as one 16-byte and one 4-byte access, without scratch memory.
 usage: python tools/check_isa.py [lib.so]   (exit code 1 on a violation; run by density_amd.build)"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,6 +48,27 @@ def check_function(name, rounds, body, top=256):
         print(f"{name}: no hand-issued loads found")
         bad += 1
     return loads, bad
+
+def kernel_meta(notes, kern):
+    """(name, scratch bytes, VGPRs, VGPRs spilled) of every kernel whose name contains `kern`, from the code objects' metadata notes."""
+    for m in re.finditer(r"\.name:\s+(\S*" + kern + r"\S*)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_spill_count:\s+(\d+)", notes):
+        yield m.group(1), int(m.group(2)), int(m.group(3)), int(m.group(4))
+
+def row_pairs(body):
+    """Loads and stores that move 20 bytes as a dwordx4 and a dword at offset:16 from the same address (registers and base), within a few instructions."""
+    acc = re.compile(r"^global_(load|store)_dword(x4)? (\S+), (\S+), (off|s\[\d+:\d+\])(?: offset:(-?\d+))?")
+    found = {"load": 0, "store": 0}
+    parsed = [acc.match(t) for t in body]
+    for k, m in enumerate(parsed):
+        if not m or not m.group(2):
+            continue
+        kind, off = m.group(1), int(m.group(6) or 0)
+        addr = (m.group(3) if kind == "store" else m.group(4), m.group(5))
+        for u in parsed[max(0, k - 4):k + 5]:
+            if u and not u.group(2) and u.group(1) == kind and (u.group(3) if kind == "store" else u.group(4), u.group(5)) == addr and int(u.group(6) or 0) == off + 16:
+                found[kind] += 1
+                break
+    return found
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 
@@ -156,15 +178,33 @@ def main():
     # exchange_stages.hip: eight waves of a stage work-group share a CU, two per SIMD — 256 registers each.  A stage kernel that needs
     # more spills to scratch memory inside the token's critical path without a test failing.
     stages = 0
-    for m in re.finditer(r"\.name:\s+(\S*exchange_stage\S*)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_spill_count:\s+(\d+)", notes):
+    for name, scratch, vgprs, spills in kernel_meta(notes, "exchange_stage"):
         stages += 1
-        if int(m.group(2)) or int(m.group(4)) or int(m.group(3)) > 256:
-            print(f"{m.group(1)}: scratch {m.group(2)} bytes, {m.group(3)} registers, {m.group(4)} spilled")
+        if scratch or spills or vgprs > 256:
+            print(f"{name}: scratch {scratch} bytes, {vgprs} registers, {spills} spilled")
             bad += 1
     if not stages:
         print("check_isa: no exchange stage kernels found")
         bad += 1
-    print(f"check_isa: {os.path.basename(lib)}: {total} hand-issued loads in the encoder instances with kept quads, decoder waits checked, {stages} exchange stage kernels without scratch, {bad} violation(s)")
+    # Lion (serial_codec.hip: row_load / row_store): at three streams a CU the kernels are bound by the number of requests the memory system takes, so a
+    # prediction row moves as a 16-byte and a 4-byte access at offset:16 from the same address — two memory instructions, not five
+    rows = 0
+    for kern in ("lion_encode_wave", "lion_decode_pair"):
+        name = next((n for n in funcs if kern in n), None)
+        if name is None:
+            print(f"check_isa: {kern} not found")
+            bad += 1
+            continue
+        pairs = row_pairs(funcs[name])
+        if not pairs["load"] or not pairs["store"]:
+            print(f"{name}: no row moved as 16 + 4 bytes ({pairs['load']} loads, {pairs['store']} stores)")
+            bad += 1
+        rows += pairs["load"] + pairs["store"]
+        meta = list(kernel_meta(notes, kern))
+        if not meta or any(scratch or spills for _, scratch, _, spills in meta):
+            print(f"{name}: scratch / spilled registers: {[(scratch, spills) for _, scratch, _, spills in meta] or 'no metadata found'}")
+            bad += 1
+    print(f"check_isa: {os.path.basename(lib)}: {total} hand-issued loads in the encoder instances with kept quads, decoder waits checked, {stages} exchange stage kernels without scratch, {rows} Lion row accesses of 16 + 4 bytes, {bad} violation(s)")
     return 1 if bad or not total else 0
 
 if __name__ == "__main__":
