@@ -1,6 +1,8 @@
 """GPU parity tests for Cheetah and Lion (density_amd/csrc/serial_codec.hip, exchange_stages.hip) through the same C ABI, bit-exact
 against the CPU oracle: every test runs on the default kernels (one wave per stream; containers of 64 / 128 KiB chunks and more encode
-in passes of ordered LDS exchanges), on the one-lane-per-stream kernels (kernel variant 16) and with the exchange passes off (variant 32)."""
+in passes of ordered LDS exchanges), on the one-lane-per-stream kernels (kernel variant 16) and with the exchange passes off (variant 32).
+Lion's DECODERS on containers assembled on the CPU, on inputs whose prediction rows move within a step, on every length across a step boundary
+and on corrupt streams: tests/test_gpu_lion_decode.py (Cheetah's: tests/test_gpu_decode_passes.py)."""
 import hashlib
 import json
 import os
