@@ -1,7 +1,8 @@
 // api.hip — the C ABI of libdensity_hip.so (include/density_hip.h), first of three units: per-device context, workspace plans, the
-// container's device-side drivers and the device-pointer / bookkeeping entry points.  (api_stream.hip: one reference stream — the
-// reference's nine symbols; api_host.hip: the host-pointer container calls.)  No CPU codec lives here: every byte is produced by the
-// gfx950 kernels, and every entry point fails (returns 0 / an error code) when no usable HIP device is present.
+// container's device-side drivers (encode in its three forms, decode, pack) and the device-pointer / bookkeeping entry points.
+// (api_stream.hip: one reference stream, from device and from host pointers; api_host.hip: the host-pointer container calls.)  No CPU
+// codec lives here: every byte is produced by the gfx950 kernels, and every entry point fails (returns 0 / an error code) when no usable
+// HIP device is present.
 #include "api_internal.hpp"
 
 namespace density {
@@ -114,20 +115,16 @@ hipError_t codec_decode(int algo, const uint8_t* d_in, const uint64_t* d_offsets
 const char* encode_kernel_name(int algo) { return algo == DENSITY_HIP_CHAMELEON ? "chameleon_encode_chunks" : algo == DENSITY_HIP_CHEETAH ? "cheetah_encode_chunks" : "lion_encode_chunks"; }
 const char* decode_kernel_name(int algo) { return algo == DENSITY_HIP_CHAMELEON ? "chameleon_decode_chunks" : algo == DENSITY_HIP_CHEETAH ? "cheetah_decode_chunks" : "lion_decode_chunks"; }
 
-size_t container_bound(int algo, size_t n, size_t chunk) {
+// every payload but the last `stride` bytes from the next, the last one as long as its chunk can get
+static size_t bound_at_stride(int algo, size_t n, size_t chunk, size_t stride) {
     const size_t nc = chunk_count(n, chunk);
-    size_t bound = payload_base(nc, n, true);      // an upper bound for both flavours
-    if (nc) bound += (nc - 1) * align_up(safe_size(algo, chunk), 16) + safe_size(algo, n - (nc - 1) * chunk);
+    size_t bound = payload_base(nc, n, true);      // (with the block index: an upper bound for both flavours)
+    if (nc) bound += (nc - 1) * stride + safe_size(algo, n - (nc - 1) * chunk);
     return bound;
 }
-
-// a slotted container: every payload in its worst-case slot (the last one as long as its chunk can get)
-size_t container_bound_slotted(int algo, size_t n, size_t chunk) {
-    const size_t nc = chunk_count(n, chunk);
-    size_t bound = payload_base(nc, n, true);
-    if (nc) bound += (nc - 1) * slot_stride(algo, chunk) + safe_size(algo, n - (nc - 1) * chunk);
-    return bound;
-}
+size_t container_bound(int algo, size_t n, size_t chunk) { return bound_at_stride(algo, n, chunk, align_up(safe_size(algo, chunk), 16)); }
+// a slotted container: every payload in its worst-case slot
+size_t container_bound_slotted(int algo, size_t n, size_t chunk) { return bound_at_stride(algo, n, chunk, slot_stride(algo, chunk)); }
 
 // a paged container: every chunk as many pages as its worst case needs (they are taken as the streams grow: a container of text ends far below this)
 size_t container_bound_paged(int algo, size_t n, size_t chunk) {
@@ -153,89 +150,99 @@ int check_header(const density_hip_header_t& h, size_t container_size) {
 
 // ---- device-side drivers (ctx already acquired; `ws` points at a workspace of sufficient size) ----
 
+hipError_t encode_slice(const EncodePlan& p, uint8_t* ws, const uint8_t* d_in, const Slice& sl, bool is_first, bool is_last, const density_hip_header_t& hdr,
+                        uint8_t* d_out, uint64_t cap, hipStream_t s, Profiler* prof, hipEvent_t predecessor) {
+    const bool with_index = hdr.flags & DENSITY_HIP_FLAG_BLOCK_INDEX;
+    uint8_t* d_index = with_index ? d_out + index_base(p.n_chunks) : nullptr;
+    uint32_t* d_zmap = p.zmap(ws);
+    hipError_t e = codec_encode(hdr.algo, d_in + sl.off, sl.len, p.chunk, sl.count, p.slots(ws) + (uint64_t)sl.first * p.stride, p.stride, p.sizes(ws) + sl.first,
+                                d_index ? d_index + sl.off / 256 : nullptr, p.tables(ws), d_zmap ? d_zmap + (uint64_t)sl.first * kZmapWordsPerChunk : nullptr, p.stage(ws), p.err(ws), s);
+    if (prof) prof->mark(encode_kernel_name(hdr.algo));
+    if (e == hipSuccess && predecessor) e = hipStreamWaitEvent(s, predecessor, 0);
+    if (e == hipSuccess) e = launch_layout_encode_batch(p.sizes(ws), sl.first, sl.count, is_first, is_last, hdr, payload_base(p.n_chunks, hdr.total_len, with_index), d_out, cap,
+                                                        p.offsets(ws), p.carry(ws), p.err(ws), s);
+    if (prof) prof->mark("layout_encode");
+    return e;
+}
+hipError_t gather_slice(const EncodePlan& p, uint8_t* ws, const Slice& sl, bool is_last, uint8_t* d_out, hipStream_t s) {
+    return launch_compact(p.slots(ws) + (uint64_t)sl.first * p.stride, p.stride, p.sizes(ws) + sl.first, p.offsets(ws) + sl.first, sl.count, d_out, p.err(ws), s, !is_last);
+}
+
+namespace {
+// The form a container is actually written in: what the paged form is not for goes to the slotted one, and one chunk encodes straight into place either way.
+Form settle_form(Form want, int algo, const uint8_t* d_in, size_t n, size_t chunk, size_t n_chunks) {
+    if (want == Form::Paged && !(paged_eligible(algo, n, chunk) && rotor_encode_eligible(d_in, n, chunk, (uint32_t)n_chunks) && !g_rotor_unsafe && !variant(kVarNoRotor))) want = Form::Slotted;
+    if (want == Form::Slotted && n_chunks <= 1) want = Form::Packed;
+    return want;
+}
+}  // namespace
+
 int run_encode_container(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, size_t chunk,
-                         uint8_t* ws, hipStream_t s, density_hip_header_t* header_out, bool slotted, bool paged) {
+                         uint8_t* ws, hipStream_t s, density_hip_header_t* header_out, Form form) {
     const EncodePlan p = plan_encode(algo, n, chunk);
     if (p.n_chunks > 0xffffffffull) { set_error("too many chunks"); return DENSITY_HIP_ERR_ARGUMENT; }
-    if (p.n_chunks <= 1) slotted = false;                                              // (one chunk encodes straight into place either way)
-    if (paged && !(paged_eligible(algo, n, chunk) && rotor_encode_eligible(d_in, n, chunk, (uint32_t)p.n_chunks) && !g_rotor_unsafe && !(g_variant & 5))) { paged = false; slotted = p.n_chunks > 1; }   // (what the paged form is not for: the slotted one)
-    if (cap < (paged ? container_bound_paged(algo, n, chunk) : slotted ? container_bound_slotted(algo, n, chunk) : container_bound(algo, n, chunk))) { set_error("output capacity below density_hip_container_bound()"); return DENSITY_HIP_ERR_CAPACITY; }
-    uint32_t* d_err = reinterpret_cast<uint32_t*>(ws + p.off_err);
-    uint64_t* d_sizes = reinterpret_cast<uint64_t*>(ws + p.off_sizes);
-    uint64_t* d_offsets = reinterpret_cast<uint64_t*>(ws + p.off_offsets);
-    uint8_t* d_slots = ws + p.off_slots;
-    uint32_t* d_zmap = zmap_bytes(algo, p.n_chunks) ? reinterpret_cast<uint32_t*>(ws + p.off_zmap) : nullptr;
-    density_hip_header_t hdr{};
-    hdr.magic = DENSITY_HIP_MAGIC; hdr.algo = (uint8_t)algo; hdr.version = 1; hdr.flags = (want_index(algo) ? DENSITY_HIP_FLAG_BLOCK_INDEX : 0) | (slotted ? DENSITY_HIP_FLAG_SLOTTED : 0);
-    hdr.chunk_size = (uint32_t)chunk; hdr.n_chunks = (uint32_t)p.n_chunks; hdr.total_len = n; hdr.container_len = 0;
-
+    form = settle_form(form, algo, d_in, n, chunk, p.n_chunks);
+    const size_t bound = form == Form::Paged ? container_bound_paged(algo, n, chunk) : form == Form::Slotted ? container_bound_slotted(algo, n, chunk) : container_bound(algo, n, chunk);
+    if (cap < bound) { set_error("output capacity below density_hip_container_bound()"); return DENSITY_HIP_ERR_CAPACITY; }
+    const uint32_t nch = (uint32_t)p.n_chunks;
+    uint32_t* d_err = p.err(ws);
+    uint64_t* d_sizes = p.sizes(ws);
+    const density_hip_header_t hdr = make_header(algo, chunk, nch, n, (want_index(algo) ? DENSITY_HIP_FLAG_BLOCK_INDEX : 0) |
+                                                 (form == Form::Slotted ? DENSITY_HIP_FLAG_SLOTTED : form == Form::Paged ? DENSITY_HIP_FLAG_PAGED : 0));
     const bool with_index = hdr.flags & DENSITY_HIP_FLAG_BLOCK_INDEX;
-    const uint64_t pbase = payload_base(p.n_chunks, n, with_index);
-    uint8_t* d_index = with_index ? d_out + index_base(p.n_chunks) : nullptr;
+    const uint64_t pbase = payload_base(nch, n, with_index);
+    uint8_t* d_index = with_index ? d_out + index_base(nch) : nullptr;
     Profiler prof(c, s);
     hipError_t e = hipMemsetAsync(d_err, 0, sizeof(uint32_t), s);
     if (e != hipSuccess) { set_error("hipMemsetAsync", e); return DENSITY_HIP_ERR_RUNTIME; }
-    if (paged) {
+    if (form == Form::Paged) {
         // Paged container (round 5): the wire form WITHOUT a stitch.  The encode kernel places the streams itself, page by page (64 KiB, from one
         // counter, in the order the chunks ask for them): dense but for the unused tails of the pages, and a chunk's stream is its pages' used bytes
         // in directory order.  write_buffer.rs:29-31's running total lives in the directory.
-        hdr.flags = DENSITY_HIP_FLAG_BLOCK_INDEX | DENSITY_HIP_FLAG_PAGED;
-        const uint64_t dir_base = paged_dir_base(p.n_chunks, n), pages_base = paged_pages_base(p.n_chunks, n, chunk);
+        const uint64_t dir_base = paged_dir_base(nch, n), pages_base = paged_pages_base(nch, n, chunk);
         const uint32_t ppc = paged_pages_per_chunk(chunk);
-        uint32_t* d_counter = d_err + 4;
+        uint32_t* d_counter = p.page_counter(ws);
         e = hipMemsetAsync(d_counter, 0, sizeof(uint32_t), s);
-        if (e == hipSuccess) e = launch_rotor_encode_paged(d_in, n, chunk, (uint32_t)p.n_chunks, d_out + pages_base, (uint32_t)std::min<uint64_t>((cap - pages_base) / kPageBytes, 0xffffu),
+        if (e == hipSuccess) e = launch_rotor_encode_paged(d_in, n, chunk, nch, d_out + pages_base, (uint32_t)std::min<uint64_t>((cap - pages_base) / kPageBytes, 0xffffu),
                                                          d_counter, reinterpret_cast<uint32_t*>(d_out + dir_base), page_dir_words(ppc), d_sizes, d_index, d_err, s);
         prof.mark(encode_kernel_name(algo));
-        if (e == hipSuccess) e = launch_layout_encode_paged(d_sizes, (uint32_t)p.n_chunks, hdr, dir_base, dir_base + paged_dir_bytes(p.n_chunks, chunk), pages_base, d_out, cap, d_counter, d_err, s);
+        if (e == hipSuccess) e = launch_layout_encode_paged(d_sizes, nch, hdr, dir_base, dir_base + paged_dir_bytes(nch, chunk), pages_base, d_out, cap, d_counter, d_err, s);
         prof.mark("layout_encode");
-    } else if (p.n_chunks == 1) {
-        // single chunk: its stream goes straight to its final place, no stitch pass
-        e = codec_encode(algo, d_in, n, chunk, 1, d_out + pbase, 0, d_sizes, d_index, ws + p.off_tables, d_zmap, p.total > p.off_stage ? ws + p.off_stage : nullptr, d_err, s);
+    } else if (nch == 1 || form == Form::Slotted) {
+        // The chunk streams stay where the encoder puts them, no stitch pass.  A single chunk: its stream goes straight to its final place.
+        // Slotted container: worst-case slots INSIDE the container, at payload_base + i * slot_stride, and the size table says how much of each
+        // slot is stream.  No gather: the decoder reads the slots through the same arithmetic; the packed wire form is made when the
+        // container leaves the device (density_hip_pack_device: a copy happens there anyway).
+        const uint64_t stride = nch == 1 ? 0 : p.stride;
+        e = codec_encode(algo, d_in, n, chunk, nch, d_out + pbase, stride, d_sizes, d_index, p.tables(ws), p.zmap(ws), p.stage(ws), d_err, s);
         prof.mark(encode_kernel_name(algo));
-        if (e == hipSuccess) e = launch_layout_encode(d_sizes, 1, hdr, pbase, d_out, cap, d_offsets, d_err, s);
-        prof.mark("layout_encode");
-    } else if (slotted) {
-        // Slotted container: the chunk streams stay where the encoder put them — worst-case slots INSIDE the container, at payload_base +
-        // i * slot_stride — and the size table says how much of each slot is stream.  No gather: the decoder reads the slots through the
-        // same arithmetic; the packed wire form is made when the container leaves the device (density_hip_pack_device: a copy happens there anyway).
-        e = codec_encode(algo, d_in, n, chunk, (uint32_t)p.n_chunks, d_out + pbase, p.stride, d_sizes, d_index, ws + p.off_tables, d_zmap,
-                         p.total > p.off_stage ? ws + p.off_stage : nullptr, d_err, s);
-        prof.mark(encode_kernel_name(algo));
-        if (e == hipSuccess) e = launch_layout_encode(d_sizes, (uint32_t)p.n_chunks, hdr, pbase, d_out, cap, d_offsets, d_err, s, p.stride);
+        if (e == hipSuccess) e = launch_layout_encode(d_sizes, nch, hdr, pbase, d_out, cap, p.offsets(ws), d_err, s, stride);
         prof.mark("layout_encode");
     } else {
         // Chunk streams go to worst-case slots; their sizes are known only afterwards (write_buffer.rs:29-31 keeps a running total: in
-        // parallel an exclusive scan), then the streams are gathered into the packed container.  Optional (kernel variant bit 3, measured, not
+        // parallel an exclusive scan), then the streams are gathered into the packed container.  Optional (kVarBatchedStitch, measured, not
         // the default): large inputs encoded in up to kStitchBatches batches of whole multiples of 256 chunks (one per CU) with the gather of
         // batch k on a second stream beside the encoding of batch k+1.  It hides the gather but the encoder — whose dictionary chain is
         // sensitive to load latency — slows down by as much (0.68 + 0.10 ms against 0.56 + 0.25 ms per GiB): DESIGN.md.
         constexpr uint32_t kStitchBatches = 4;
-        const uint32_t nch = (uint32_t)p.n_chunks;
         uint32_t per = nch, batches = 1;
-        if (algo == DENSITY_HIP_CHAMELEON && nch >= 512 && (g_variant & 8)) {
+        if (algo == DENSITY_HIP_CHAMELEON && nch >= 512 && variant(kVarBatchedStitch)) {
             batches = nch / 256 < kStitchBatches ? nch / 256 : kStitchBatches;
             per = ((nch + batches - 1) / batches + 255) / 256 * 256;
             batches = (nch + per - 1) / per;
         }
-        uint64_t* d_carry = d_offsets + p.n_chunks;                      // (the extra entry of the offsets array)
         for (uint32_t k = 0; k < batches && e == hipSuccess; ++k) {
-            const uint32_t first = k * per, count = (first + per <= nch) ? per : nch - first;
-            const uint64_t in_off = (uint64_t)first * chunk;
-            e = codec_encode(algo, d_in + in_off, n - in_off < (uint64_t)count * chunk ? n - in_off : (uint64_t)count * chunk, chunk, count, d_slots + (uint64_t)first * p.stride,
-                             p.stride, d_sizes + first, d_index ? d_index + in_off / 256 : nullptr, ws + p.off_tables,
-                             d_zmap ? d_zmap + (uint64_t)first * kZmapWordsPerChunk : nullptr, p.total > p.off_stage ? ws + p.off_stage : nullptr, d_err, s);
-            prof.mark(encode_kernel_name(algo));
-            if (e == hipSuccess) e = launch_layout_encode_batch(d_sizes, first, count, k == 0, k + 1 == batches, hdr, pbase, d_out, cap, d_offsets, d_carry, d_err, s);
-            prof.mark("layout_encode");
+            const Slice sl = slice_of(k, per, nch, chunk, n);
+            const bool is_last = k + 1 == batches;
+            e = encode_slice(p, ws, d_in, sl, k == 0, is_last, hdr, d_out, cap, s, &prof, nullptr);
             if (e != hipSuccess) break;
             if (batches == 1) {
-                e = launch_compact(d_slots, p.stride, d_sizes, d_offsets, count, d_out, d_err, s);
+                e = gather_slice(p, ws, sl, is_last, d_out, s);
                 prof.mark("compact");
             } else {
                 e = hipEventRecord(c->batch_done[k], s);
                 if (e == hipSuccess) e = hipStreamWaitEvent(c->stitch_stream, c->batch_done[k], 0);
-                if (e == hipSuccess) e = launch_compact(d_slots + (uint64_t)first * p.stride, p.stride, d_sizes + first, d_offsets + first, count, d_out, d_err, c->stitch_stream, k + 1 < batches);
+                if (e == hipSuccess) e = gather_slice(p, ws, sl, is_last, d_out, c->stitch_stream);
             }
         }
         if (e == hipSuccess && batches > 1) {                               // the caller's stream continues when the last gather is done
@@ -247,9 +254,7 @@ int run_encode_container(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, 
     if (e != hipSuccess) { set_error("kernel launch (encode)", e); return DENSITY_HIP_ERR_RUNTIME; }
     if (header_out) {
         uint32_t h_err = 0;
-        e = hipMemcpyAsync(header_out, d_out, sizeof(*header_out), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        e = read_back(s, d_err, &h_err, header_out, d_out, sizeof(*header_out));
         if (e != hipSuccess) { set_error("encode (device)", e); return DENSITY_HIP_ERR_RUNTIME; }
         if (h_err & 16u) { set_error("encode: device-side watchdog"); return DENSITY_HIP_ERR_RUNTIME; }
         if (h_err) { set_error("container does not fit the output capacity"); return DENSITY_HIP_ERR_CAPACITY; }
@@ -261,18 +266,15 @@ int run_decode_container(DeviceCtx* c, const uint8_t* d_in, size_t container_siz
                          size_t cap, uint8_t* ws, hipStream_t s, size_t* decoded_out, size_t ws_size) {
     if (cap < h.total_len) { set_error("output capacity below the container's total_len"); return DENSITY_HIP_ERR_CAPACITY; }
     const DecodePlan p = plan_decode(h.algo, h.n_chunks, h.chunk_size);
-    uint8_t* d_pass = (ws_size >= p.total_with_passes && p.total_with_passes > p.total) ? ws + p.off_pass : nullptr;   // (a caller's smaller workspace: the one-wave decoder)
-    uint32_t* d_err = reinterpret_cast<uint32_t*>(ws + p.off_err);
-    uint64_t* d_sizes = reinterpret_cast<uint64_t*>(ws + p.off_sizes);
-    uint64_t* d_offsets = reinterpret_cast<uint64_t*>(ws + p.off_offsets);
-    uint64_t* d_produced = reinterpret_cast<uint64_t*>(ws + p.off_produced);
+    uint32_t* d_err = p.err(ws);
+    uint64_t *d_sizes = p.sizes(ws), *d_offsets = p.offsets(ws), *d_produced = p.produced(ws);
+    uint32_t* d_zmap = p.zmap(ws);
     Profiler prof(c, s);
     hipError_t e = hipMemsetAsync(d_err, 0, sizeof(uint32_t), s);
     const bool with_index = h.flags & DENSITY_HIP_FLAG_BLOCK_INDEX;
     const uint8_t* d_index = with_index ? d_in + index_base(h.n_chunks) : nullptr;
     if (h.flags & DENSITY_HIP_FLAG_PAGED) {
         // the pages are read where they lie: the rotation decoder turns stream positions into page offsets through the chunk's directory
-        uint32_t* d_zmap = zmap_bytes(h.algo, h.n_chunks) ? reinterpret_cast<uint32_t*>(ws + p.off_zmap) : nullptr;
         const size_t dir_base = paged_dir_base(h.n_chunks, h.total_len), pages_base = paged_pages_base(h.n_chunks, h.total_len, h.chunk_size);
         if (g_rotor_unsafe || !rotor_decode_eligible(d_out, h.n_chunks, h.chunk_size, h.total_len, d_index, d_zmap) || (uintptr_t)(d_in + pages_base) % 4 != 0) {
             set_error("a paged container needs the rotation decoder (chunks of at most 4 MiB, 4-byte aligned buffers)"); return DENSITY_HIP_ERR_UNSUPPORTED;
@@ -284,17 +286,17 @@ int run_decode_container(DeviceCtx* c, const uint8_t* d_in, size_t container_siz
                                                          (uint32_t)((h.container_len - pages_base) / kPageBytes), d_zmap, d_produced, d_err, s);
         prof.mark(decode_kernel_name(h.algo));
     } else {
-    if (e == hipSuccess) e = launch_layout_decode(d_in, container_size, h.n_chunks, payload_base(h.n_chunks, h.total_len, with_index), d_sizes, d_offsets, d_err, s,
-                                                  (h.flags & DENSITY_HIP_FLAG_SLOTTED) ? slot_stride(h.algo, h.chunk_size) : 0);
-    prof.mark("layout_decode");
-    if (e == hipSuccess) e = codec_decode(h.algo, d_in, d_offsets, d_sizes, h.n_chunks, d_out, h.chunk_size, h.total_len, true, d_index, d_produced, d_err, ws + p.off_tables, zmap_bytes(h.algo, h.n_chunks) ? reinterpret_cast<uint32_t*>(ws + p.off_zmap) : nullptr, s, d_pass);
-    prof.mark(decode_kernel_name(h.algo));
+        if (e == hipSuccess) e = launch_layout_decode(d_in, container_size, h.n_chunks, payload_base(h.n_chunks, h.total_len, with_index), d_sizes, d_offsets, d_err, s,
+                                                      (h.flags & DENSITY_HIP_FLAG_SLOTTED) ? slot_stride(h.algo, h.chunk_size) : 0);
+        prof.mark("layout_decode");
+        if (e == hipSuccess) e = codec_decode(h.algo, d_in, d_offsets, d_sizes, h.n_chunks, d_out, h.chunk_size, h.total_len, true, d_index, d_produced, d_err, p.tables(ws), d_zmap, s,
+                                              p.pass(ws, ws_size));
+        prof.mark(decode_kernel_name(h.algo));
     }
     if (e != hipSuccess) { set_error("kernel launch (decode)", e); return DENSITY_HIP_ERR_RUNTIME; }
     if (decoded_out) {
         uint32_t h_err = 0;
-        e = hipMemcpyAsync(&h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        e = read_back(s, d_err, &h_err);
         if (e != hipSuccess) { set_error("decode (device)", e); return DENSITY_HIP_ERR_RUNTIME; }
         if (h_err) { set_error("malformed or truncated container payload"); *decoded_out = 0; return DENSITY_HIP_ERR_FORMAT; }
         *decoded_out = h.total_len;
@@ -306,10 +308,9 @@ int run_decode_container(DeviceCtx* c, const uint8_t* d_in, size_t container_siz
 int run_pack_container(DeviceCtx* c, const uint8_t* d_in, size_t container_size, const density_hip_header_t& h, uint8_t* d_out, size_t cap, uint8_t* ws,
                        hipStream_t s, density_hip_header_t* header_out) {
     const DecodePlan p = plan_decode(h.algo, h.n_chunks);
-    uint32_t* d_err = reinterpret_cast<uint32_t*>(ws + p.off_err);
-    uint64_t* d_sizes = reinterpret_cast<uint64_t*>(ws + p.off_sizes);
-    uint64_t* d_offsets = reinterpret_cast<uint64_t*>(ws + p.off_offsets);
-    uint64_t* d_sizes64 = reinterpret_cast<uint64_t*>(ws + p.off_produced);           // (the u64 sizes the layout kernel wants)
+    uint32_t* d_err = p.err(ws);
+    uint64_t *d_sizes = p.sizes(ws), *d_offsets = p.offsets(ws);
+    uint64_t* d_sizes64 = p.produced(ws);                                              // (the u64 sizes the layout kernel wants)
     const bool with_index = h.flags & DENSITY_HIP_FLAG_BLOCK_INDEX;
     const uint64_t pbase = payload_base(h.n_chunks, h.total_len, with_index);
     if (cap < container_bound(h.algo, h.total_len, h.chunk_size)) { set_error("output capacity below density_hip_container_bound()"); return DENSITY_HIP_ERR_CAPACITY; }
@@ -333,14 +334,40 @@ int run_pack_container(DeviceCtx* c, const uint8_t* d_in, size_t container_size,
     if (e != hipSuccess) { set_error("kernel launch (pack)", e); return DENSITY_HIP_ERR_RUNTIME; }
     if (header_out) {
         uint32_t h_err = 0;
-        e = hipMemcpyAsync(header_out, d_out, sizeof(*header_out), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        e = read_back(s, d_err, &h_err, header_out, d_out, sizeof(*header_out));
         if (e != hipSuccess) { set_error("pack (device)", e); return DENSITY_HIP_ERR_RUNTIME; }
         if (h_err) { set_error("malformed slotted container"); return DENSITY_HIP_ERR_FORMAT; }
     }
     return DENSITY_HIP_OK;
 }
+
+namespace {
+// the three density_hip_encode_device* symbols: they differ in the form asked for
+int encode_device(Form form, int algo, const void* d_input, size_t input_size, void* d_output, size_t output_capacity, size_t chunk_size, void* d_workspace,
+                  size_t workspace_size, void* stream, density_hip_header_t* header_out) {
+    g_last_error.clear();
+    if (!take_geometry(algo, input_size, &chunk_size) || (!d_input && input_size) || !d_output) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return DENSITY_HIP_ERR_RUNTIME;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const size_t need = plan_encode(algo, input_size, chunk_size).total;
+    uint8_t* ws = nullptr;
+    if (const int rc = resolve_workspace(c, d_workspace, workspace_size, need, need, &ws)) return rc;
+    return run_encode_container(c, algo, (const uint8_t*)d_input, input_size, (uint8_t*)d_output, output_capacity, chunk_size, ws, stream ? (hipStream_t)stream : c->stream, header_out, form);
+}
+// the header of a container on the device: the caller's copy, or read back on s — ordered behind whatever produced the container on the caller's
+// stream (streams here are non-blocking: a plain hipMemcpy is not) — and checked against the container's size
+int container_header(const density_hip_header_t* header, const void* d_container, size_t container_size, hipStream_t s, density_hip_header_t* h) {
+    if (header) *h = *header;
+    else {
+        hipError_t e = hipMemcpyAsync(h, d_container, sizeof(*h), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { set_error("header read-back", e); return DENSITY_HIP_ERR_RUNTIME; }
+    }
+    if (check_header(*h, container_size) != DENSITY_HIP_OK) { set_error("bad container header"); return DENSITY_HIP_ERR_FORMAT; }
+    return DENSITY_HIP_OK;
+}
+}  // namespace
 
 }  // namespace api
 }  // namespace density
@@ -352,15 +379,11 @@ extern "C" {
 
 // ---- section 2: container + device API ----
 size_t density_hip_container_bound(int algo, size_t input_size, size_t chunk_size) {
-    chunk_size = normalise_chunk(chunk_size, input_size, algo);
-    if (!valid_algo(algo) || !valid_chunk(chunk_size)) return 0;
-    return container_bound(algo, input_size, chunk_size);
+    return take_geometry(algo, input_size, &chunk_size) ? container_bound(algo, input_size, chunk_size) : 0;
 }
 
 size_t density_hip_encode_workspace_size(int algo, size_t input_size, size_t chunk_size) {
-    chunk_size = normalise_chunk(chunk_size, input_size, algo);
-    if (!valid_algo(algo) || !valid_chunk(chunk_size)) return 0;
-    return plan_encode(algo, input_size, chunk_size).total;
+    return take_geometry(algo, input_size, &chunk_size) ? plan_encode(algo, input_size, chunk_size).total : 0;
 }
 
 size_t density_hip_decode_workspace_size(uint32_t n_chunks) {   // the largest of the three algorithms
@@ -368,73 +391,29 @@ size_t density_hip_decode_workspace_size(uint32_t n_chunks) {   // the largest o
     return a > b ? a : b;
 }
 
-int density_hip_encode_device(int algo, const void* d_input, size_t input_size, void* d_output, size_t output_capacity,
-                              size_t chunk_size, void* d_workspace, size_t workspace_size, void* stream,
-                              density_hip_header_t* header_out) {
-    g_last_error.clear();
-    chunk_size = normalise_chunk(chunk_size, input_size, algo);
-    if (!valid_algo(algo) || !valid_chunk(chunk_size) || (!d_input && input_size) || !d_output) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
-    DeviceCtx* c = acquire_ctx();
-    if (!c) return DENSITY_HIP_ERR_RUNTIME;
-    std::lock_guard<std::mutex> lk(c->mu);
-    const size_t need = plan_encode(algo, input_size, chunk_size).total;
-    uint8_t* ws = (uint8_t*)d_workspace;
-    if (ws) { if (workspace_size < need) { set_error("workspace too small"); return DENSITY_HIP_ERR_CAPACITY; } }
-    else { hipError_t e = c->work.ensure(need); if (e != hipSuccess) { set_error("workspace allocation", e); return DENSITY_HIP_ERR_RUNTIME; } ws = (uint8_t*)c->work.p; }
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return run_encode_container(c, algo, (const uint8_t*)d_input, input_size, (uint8_t*)d_output, output_capacity, chunk_size, ws, s, header_out);
-}
-
 size_t density_hip_decode_workspace_size_for(int algo, size_t total_len, size_t chunk_size) {
-    chunk_size = normalise_chunk(chunk_size, total_len, algo);
-    if (!valid_algo(algo) || !valid_chunk(chunk_size)) return 0;
-    return plan_decode(algo, chunk_count(total_len, chunk_size), chunk_size).total_with_passes;
+    return take_geometry(algo, total_len, &chunk_size) ? plan_decode(algo, chunk_count(total_len, chunk_size), chunk_size).total_with_passes : 0;
 }
 
-int density_hip_encode_device_slotted(int algo, const void* d_input, size_t input_size, void* d_output, size_t output_capacity,
-                                      size_t chunk_size, void* d_workspace, size_t workspace_size, void* stream,
-                                      density_hip_header_t* header_out) {
-    g_last_error.clear();
-    chunk_size = normalise_chunk(chunk_size, input_size, algo);
-    if (!valid_algo(algo) || !valid_chunk(chunk_size) || (!d_input && input_size) || !d_output) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
-    DeviceCtx* c = acquire_ctx();
-    if (!c) return DENSITY_HIP_ERR_RUNTIME;
-    std::lock_guard<std::mutex> lk(c->mu);
-    const size_t need = plan_encode(algo, input_size, chunk_size).total;
-    uint8_t* ws = (uint8_t*)d_workspace;
-    if (ws) { if (workspace_size < need) { set_error("workspace too small"); return DENSITY_HIP_ERR_CAPACITY; } }
-    else { hipError_t e = c->work.ensure(need); if (e != hipSuccess) { set_error("workspace allocation", e); return DENSITY_HIP_ERR_RUNTIME; } ws = (uint8_t*)c->work.p; }
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return run_encode_container(c, algo, (const uint8_t*)d_input, input_size, (uint8_t*)d_output, output_capacity, chunk_size, ws, s, header_out, true);
+int density_hip_encode_device(int algo, const void* d_input, size_t input_size, void* d_output, size_t output_capacity, size_t chunk_size,
+                              void* d_workspace, size_t workspace_size, void* stream, density_hip_header_t* header_out) {
+    return encode_device(Form::Packed, algo, d_input, input_size, d_output, output_capacity, chunk_size, d_workspace, workspace_size, stream, header_out);
 }
-
-int density_hip_encode_device_paged(int algo, const void* d_input, size_t input_size, void* d_output, size_t output_capacity,
-                                    size_t chunk_size, void* d_workspace, size_t workspace_size, void* stream,
-                                    density_hip_header_t* header_out) {
-    g_last_error.clear();
-    chunk_size = normalise_chunk(chunk_size, input_size, algo);
-    if (!valid_algo(algo) || !valid_chunk(chunk_size) || (!d_input && input_size) || !d_output) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
-    DeviceCtx* c = acquire_ctx();
-    if (!c) return DENSITY_HIP_ERR_RUNTIME;
-    std::lock_guard<std::mutex> lk(c->mu);
-    const size_t need = plan_encode(algo, input_size, chunk_size).total;
-    uint8_t* ws = (uint8_t*)d_workspace;
-    if (ws) { if (workspace_size < need) { set_error("workspace too small"); return DENSITY_HIP_ERR_CAPACITY; } }
-    else { hipError_t e = c->work.ensure(need); if (e != hipSuccess) { set_error("workspace allocation", e); return DENSITY_HIP_ERR_RUNTIME; } ws = (uint8_t*)c->work.p; }
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return run_encode_container(c, algo, (const uint8_t*)d_input, input_size, (uint8_t*)d_output, output_capacity, chunk_size, ws, s, header_out, false, true);
+int density_hip_encode_device_slotted(int algo, const void* d_input, size_t input_size, void* d_output, size_t output_capacity, size_t chunk_size,
+                                      void* d_workspace, size_t workspace_size, void* stream, density_hip_header_t* header_out) {
+    return encode_device(Form::Slotted, algo, d_input, input_size, d_output, output_capacity, chunk_size, d_workspace, workspace_size, stream, header_out);
+}
+int density_hip_encode_device_paged(int algo, const void* d_input, size_t input_size, void* d_output, size_t output_capacity, size_t chunk_size,
+                                    void* d_workspace, size_t workspace_size, void* stream, density_hip_header_t* header_out) {
+    return encode_device(Form::Paged, algo, d_input, input_size, d_output, output_capacity, chunk_size, d_workspace, workspace_size, stream, header_out);
 }
 size_t density_hip_paged_pages_per_chunk(size_t chunk_size) { return valid_chunk(chunk_size) ? paged_pages_per_chunk(chunk_size) : 0; }
 size_t density_hip_container_bound_paged(int algo, size_t input_size, size_t chunk_size) {
-    if (!valid_algo(algo)) return 0;
-    chunk_size = normalise_chunk(chunk_size, input_size, algo);
-    if (!valid_chunk(chunk_size)) return 0;
-    return container_bound_paged(algo, input_size, chunk_size);
+    return take_geometry(algo, input_size, &chunk_size) ? container_bound_paged(algo, input_size, chunk_size) : 0;
 }
 
 size_t density_hip_container_bound_slotted(int algo, size_t input_size, size_t chunk_size) {
-    chunk_size = normalise_chunk(chunk_size, input_size, algo);
-    if (!valid_algo(algo) || !valid_chunk(chunk_size)) return 0;
+    if (!take_geometry(algo, input_size, &chunk_size)) return 0;
     const size_t a = container_bound_slotted(algo, input_size, chunk_size), b = container_bound(algo, input_size, chunk_size);
     return a > b ? a : b;
 }
@@ -448,19 +427,12 @@ int density_hip_pack_device(const void* d_container, size_t container_size, cons
     std::lock_guard<std::mutex> lk(c->mu);
     density_hip_header_t h;
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (header) h = *header;
-    else {
-        hipError_t e = hipMemcpyAsync(&h, d_container, sizeof(h), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { set_error("header read-back", e); return DENSITY_HIP_ERR_RUNTIME; }
-    }
-    if (check_header(h, container_size) != DENSITY_HIP_OK) { set_error("bad container header"); return DENSITY_HIP_ERR_FORMAT; }
+    if (const int rc = container_header(header, d_container, container_size, s, &h)) return rc;
     // a PAGED container is wire-ready as it stands, and its streams are not where the packed / slotted arithmetic looks for them
     if (h.flags & DENSITY_HIP_FLAG_PAGED) { set_error("density_hip_pack_device: a paged container is not packed (it is wire-ready; decode it or read its pages)"); return DENSITY_HIP_ERR_UNSUPPORTED; }
     const size_t need = plan_decode(h.algo, h.n_chunks).total;
-    uint8_t* ws = (uint8_t*)d_workspace;
-    if (ws) { if (workspace_size < need) { set_error("workspace too small"); return DENSITY_HIP_ERR_CAPACITY; } }
-    else { hipError_t e = c->work.ensure(need); if (e != hipSuccess) { set_error("workspace allocation", e); return DENSITY_HIP_ERR_RUNTIME; } ws = (uint8_t*)c->work.p; }
+    uint8_t* ws = nullptr;
+    if (const int rc = resolve_workspace(c, d_workspace, workspace_size, need, need, &ws)) return rc;
     return run_pack_container(c, (const uint8_t*)d_container, container_size, h, (uint8_t*)d_output, output_capacity, ws, s, header_out);
 }
 
@@ -472,21 +444,13 @@ int density_hip_decode_device(const void* d_container, size_t container_size, co
     if (!c) return DENSITY_HIP_ERR_RUNTIME;
     std::lock_guard<std::mutex> lk(c->mu);
     density_hip_header_t h;
-    if (header) h = *header;
-    else {
-        // ordered behind whatever produced the container on the caller's stream (streams here are non-blocking: a plain hipMemcpy is not)
-        hipStream_t hs = stream ? (hipStream_t)stream : c->stream;
-        hipError_t e = hipMemcpyAsync(&h, d_container, sizeof(h), hipMemcpyDeviceToHost, hs);
-        if (e == hipSuccess) e = hipStreamSynchronize(hs);
-        if (e != hipSuccess) { set_error("header read-back", e); return DENSITY_HIP_ERR_RUNTIME; }
-    }
-    if (check_header(h, container_size) != DENSITY_HIP_OK) { set_error("bad container header"); return DENSITY_HIP_ERR_FORMAT; }
-    const DecodePlan dp = plan_decode(h.algo, h.n_chunks, h.chunk_size);
-    const size_t need = dp.total;
-    uint8_t* ws = (uint8_t*)d_workspace;
-    if (ws) { if (workspace_size < need) { set_error("workspace too small"); return DENSITY_HIP_ERR_CAPACITY; } }
-    else { hipError_t e = c->work.ensure(dp.total_with_passes); if (e != hipSuccess) { set_error("workspace allocation", e); return DENSITY_HIP_ERR_RUNTIME; } ws = (uint8_t*)c->work.p; workspace_size = c->work.cap; }
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (const int rc = container_header(header, d_container, container_size, s, &h)) return rc;
+    // a caller's workspace need only hold what the one-wave decoders want (the decode passes are then left out: DecodePlan::pass); the context's own
+    // is sized for the passes, and what it holds is what the driver is told
+    const DecodePlan dp = plan_decode(h.algo, h.n_chunks, h.chunk_size);
+    uint8_t* ws = nullptr;
+    if (const int rc = resolve_workspace(c, d_workspace, workspace_size, dp.total, dp.total_with_passes, &ws, &workspace_size)) return rc;
     return run_decode_container(c, (const uint8_t*)d_container, container_size, h, (uint8_t*)d_output, output_capacity, ws, s, decoded_size_out, workspace_size);
 }
 
@@ -497,7 +461,21 @@ size_t density_hip_auto_chunk(size_t input_size) { return auto_chunk(input_size)
 size_t density_hip_auto_chunk_for(int algo, size_t input_size) { return valid_algo(algo) ? auto_chunk(input_size, algo) : 0; }
 
 void density_hip_set_profiling(int enabled) { g_profiling = enabled; }
-void density_hip_set_kernel_variant(int variant) { g_variant = variant;   /* bit 3 (8): encode in batches with the stitch of one batch beside the encoding of the next */ density::g_force_simple = (variant & 1) != 0; density::g_force_pipeline = (variant & 4) != 0; density::g_force_lane_codec = (variant & 16) != 0; density::g_force_wave_codec = (variant & 32) != 0; density::g_stage_audit = (variant & 64) != 0; density::g_force_serial_decode = (variant & 128) != 0; density::g_serial_parse = (variant & 1024) != 0; density::g_chain_walk = (variant & 4096) != 0; density::g_lion_one_wave = (variant & 32768) != 0; density::g_walk_blocks = (variant & 8192) ? 1 : (variant & 16384) ? 4 : 2; density::g_rotor_split = density::kRotorSplitDefault != ((variant & 2048) != 0); }
+void density_hip_set_kernel_variant(int variant) {
+    g_variant = variant;                 // what this layer asks through variant(): kVarNoIndex, kVarBatchedStitch, kVarPipeAlways, kVarPipeNever, kVarNoRotor
+    const auto on = [variant](int bits) { return (variant & bits) != 0; };
+    density::g_force_simple = on(kVarSimple);
+    density::g_force_pipeline = on(kVarRolePipeline);
+    density::g_force_lane_codec = on(kVarLaneCodec);
+    density::g_force_wave_codec = on(kVarWaveCodec);
+    density::g_stage_audit = on(kVarStageAudit);
+    density::g_force_serial_decode = on(kVarSerialDecode);
+    density::g_serial_parse = on(kVarSerialParse);
+    density::g_chain_walk = on(kVarChainWalk);
+    density::g_lion_one_wave = on(kVarLionOneWave);
+    density::g_walk_blocks = on(kVarWalk64) ? 1 : on(kVarWalk128) ? 4 : 2;
+    density::g_rotor_split = density::kRotorSplitDefault != on(kVarRotorOtherSplit);
+}
 
 int density_hip_last_timings(float* milliseconds, const char** names, int capacity) {
     int dev = -1;
@@ -541,10 +519,8 @@ void density_hip_shutdown(void) {
         if (hipGetDevice(&cur) != hipSuccess || hipSetDevice(d) != hipSuccess) { (void)hipGetLastError(); continue; }
         (void)hipDeviceSynchronize();
         for (Buffer* b : {&c->work, &c->stage_in, &c->stage_out, &c->seg}) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
-        if (c->pin_sizes) (void)hipHostFree(c->pin_sizes);
-        c->pin_sizes = nullptr; c->pin_sizes_cap = 0;
-        if (c->pin_meta) (void)hipHostFree(c->pin_meta);
-        c->pin_meta = nullptr; c->pin_meta_cap = 0;
+        c->pin_sizes.release();
+        c->pin_meta.release();
         for (hipEvent_t ev : c->pipe_events) (void)hipEventDestroy(ev);
         c->pipe_events.clear();
         for (hipEvent_t ev : c->events) (void)hipEventDestroy(ev);

@@ -20,15 +20,6 @@ bool pipe_streams(DeviceCtx* c, uint32_t n_events) {
     if (e != hipSuccess) { set_error("pipelined host path: streams / events", e); return false; }
     return true;
 }
-hipError_t pin_meta_ensure(DeviceCtx* c, size_t bytes) {
-    if (bytes <= c->pin_meta_cap) return hipSuccess;
-    if (c->pin_meta) (void)hipHostFree(c->pin_meta);
-    c->pin_meta = nullptr; c->pin_meta_cap = 0;
-    const size_t want = align_up(bytes + bytes / 2, 4096);
-    const hipError_t e = hipHostMalloc((void**)&c->pin_meta, want, hipHostMallocDefault);
-    if (e == hipSuccess) c->pin_meta_cap = want;
-    return e;
-}
 
 namespace {
 
@@ -51,12 +42,12 @@ inline size_t pipe_slice_bytes(size_t total, size_t chunk) {
     size_t target = total / 12;
     if (target < 10 * chunk) target = 10 * chunk;
     if (target < (2u << 20)) target = 2u << 20;
-    if (g_variant & 256) target = chunk;                                              // (tests: a slice per chunk, whatever the size)
+    if (variant(kVarPipeAlways)) target = chunk;                                             // (tests: a slice per chunk, whatever the size)
     return target;
 }
 inline bool pipe_wanted(int algo, size_t n, size_t chunk, size_t n_chunks) {
-    if (algo != DENSITY_HIP_CHAMELEON || n_chunks < 4 || (g_variant & 512)) return false;
-    return (g_variant & 256) || (n >= (32u << 20) && n >= 3 * pipe_slice_bytes(n, chunk));
+    if (algo != DENSITY_HIP_CHAMELEON || n_chunks < 4 || variant(kVarPipeNever)) return false;
+    return variant(kVarPipeAlways) || (n >= (32u << 20) && n >= 3 * pipe_slice_bytes(n, chunk));
 }
 inline uint32_t pipe_slice_chunks(size_t total, size_t chunk, size_t n_chunks) {
     const size_t target = pipe_slice_bytes(total, chunk);
@@ -91,19 +82,15 @@ size_t decode_container_pipelined(DeviceCtx* c, const uint8_t* container, const 
     const uint32_t per = pipe_slice_chunks(total, chunk, nc), slices = (nc + per - 1) / per;
     if (!pipe_streams(c, 2 + 2 * slices)) return 0;
     const DecodePlan p = plan_decode(h.algo, nc, chunk);
-    hipError_t e = c->stage_in.ensure(h.container_len);
-    if (e == hipSuccess) e = c->stage_out.ensure(total);
-    if (e == hipSuccess) e = c->work.ensure(p.total);
+    hipError_t e = ensure_staging(c, h.container_len, total, p.total);
     if (e != hipSuccess) { set_error("staging buffers", e); return 0; }
     *handled = true;
     uint8_t* d_in = (uint8_t*)c->stage_in.p;
     uint8_t* d_out = (uint8_t*)c->stage_out.p;
     uint8_t* ws = (uint8_t*)c->work.p;
-    uint32_t* d_err = reinterpret_cast<uint32_t*>(ws + p.off_err);
-    uint64_t* d_sizes = reinterpret_cast<uint64_t*>(ws + p.off_sizes);
-    uint64_t* d_offsets = reinterpret_cast<uint64_t*>(ws + p.off_offsets);
-    uint64_t* d_produced = reinterpret_cast<uint64_t*>(ws + p.off_produced);
-    uint32_t* d_zmap = zmap_bytes(h.algo, nc) ? reinterpret_cast<uint32_t*>(ws + p.off_zmap) : nullptr;
+    uint32_t* d_err = p.err(ws);
+    uint64_t *d_sizes = p.sizes(ws), *d_offsets = p.offsets(ws), *d_produced = p.produced(ws);
+    uint32_t* d_zmap = p.zmap(ws);
     const uint8_t* d_index = with_index ? d_in + index_base(nc) : nullptr;
     hipStream_t s = c->stream;
     hipEvent_t ev_head = c->pipe_events[0], ev_layout = c->pipe_events[1];
@@ -114,30 +101,25 @@ size_t decode_container_pipelined(DeviceCtx* c, const uint8_t* container, const 
     if (e == hipSuccess) e = launch_layout_decode(d_in, h.container_len, nc, pbase, d_sizes, d_offsets, d_err, s, 0);
     if (e == hipSuccess) e = hipEventRecord(ev_layout, s);
     for (uint32_t k = 0; k < slices && e == hipSuccess; ++k) {
-        const uint32_t first = k * per, count = first + per <= nc ? per : nc - first;
+        const Slice sl = slice_of(k, per, nc, chunk, total);
+        const uint32_t first = sl.first, count = sl.count;
         hipEvent_t ev_up = c->pipe_events[2 + 2 * k], ev_dec = c->pipe_events[3 + 2 * k];
         hipStream_t ks = c->kern[k & 3u];
         e = hipMemcpyAsync(d_in + offs[first], container + offs[first], offs[first + count] - offs[first], hipMemcpyHostToDevice, c->up);
         if (e == hipSuccess) e = hipEventRecord(ev_up, c->up);
         if (e == hipSuccess) e = hipStreamWaitEvent(ks, ev_layout, 0);
         if (e == hipSuccess) e = hipStreamWaitEvent(ks, ev_up, 0);
-        const uint64_t out_off = (uint64_t)first * chunk;
-        if (e == hipSuccess) e = codec_decode(h.algo, d_in, d_offsets + first, d_sizes + first, count, d_out + out_off, chunk, total - out_off, true,
-                                              d_index ? d_index + out_off / 256 : nullptr, d_produced + first, d_err, nullptr,
+        if (e == hipSuccess) e = codec_decode(h.algo, d_in, d_offsets + first, d_sizes + first, count, d_out + sl.off, chunk, total - sl.off, true,
+                                              d_index ? d_index + sl.off / 256 : nullptr, d_produced + first, d_err, nullptr,
                                               d_zmap ? d_zmap + (uint64_t)first * kZmapWordsPerChunk : nullptr, ks);
         if (e == hipSuccess) e = hipEventRecord(ev_dec, ks);
         if (e == hipSuccess) e = hipStreamWaitEvent(c->down, ev_dec, 0);
-        const uint64_t bytes = total - out_off < (uint64_t)count * chunk ? total - out_off : (uint64_t)count * chunk;
-        if (e == hipSuccess) e = hipMemcpyAsync(output + out_off, d_out + out_off, bytes, hipMemcpyDeviceToHost, c->down);
+        if (e == hipSuccess) e = hipMemcpyAsync(output + sl.off, d_out + sl.off, sl.len, hipMemcpyDeviceToHost, c->down);
         if (e == hipSuccess) e = hipStreamWaitEvent(s, ev_dec, 0);
     }
     uint32_t h_err = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost, s);
-    // (always drained: nothing may still be reading or writing the caller's buffers when they are unpinned)
-    const hipError_t e1 = hipStreamSynchronize(c->up), e2 = hipStreamSynchronize(s), e3 = hipStreamSynchronize(c->down);
-    hipError_t e4 = hipSuccess;
-    for (int i = 0; i < 4; ++i) { const hipError_t x = hipStreamSynchronize(c->kern[i]); if (x != hipSuccess) e4 = x; }
-    if (e == hipSuccess) e = e1 != hipSuccess ? e1 : e2 != hipSuccess ? e2 : e3 != hipSuccess ? e3 : e4;
+    if (e == hipSuccess) e = read_back(s, d_err, &h_err);                                                     // (s waits for every slice's kernels)
+    e = drain(e, {c->up, s, c->down, c->kern[0], c->kern[1], c->kern[2], c->kern[3]});
     if (e != hipSuccess) { set_error("decode (pipelined host path)", e); return 0; }
     if (h_err) { set_error("malformed or truncated container payload"); return 0; }
     return total;
@@ -155,30 +137,16 @@ size_t encode_container_pipelined(DeviceCtx* c, int algo, const uint8_t* input, 
     if (!pin_in || !pin_out) return 0;
     const uint32_t per = pipe_slice_chunks(n, chunk, nc), slices = (uint32_t)((nc + per - 1) / per);
     if (!pipe_streams(c, 3 * slices)) return 0;
-    hipError_t e = c->stage_in.ensure(n);
-    if (e == hipSuccess) e = c->stage_out.ensure(bound);
-    if (e == hipSuccess) e = c->work.ensure(p.total);
-    if (e == hipSuccess && c->pin_sizes_cap < slices) {
-        if (c->pin_sizes) (void)hipHostFree(c->pin_sizes);
-        c->pin_sizes = nullptr; c->pin_sizes_cap = 0;
-        e = hipHostMalloc((void**)&c->pin_sizes, 8 * (size_t)(kPipeMaxSlices + 16), hipHostMallocDefault);
-        if (e == hipSuccess) c->pin_sizes_cap = kPipeMaxSlices + 16;
-    }
+    hipError_t e = ensure_staging(c, n, bound, p.total);
+    if (e == hipSuccess) e = c->pin_sizes.ensure(8 * (size_t)slices);
     if (e != hipSuccess) { set_error("staging buffers", e); return 0; }
     *handled = true;
     uint8_t* d_in = (uint8_t*)c->stage_in.p;
     uint8_t* d_out = (uint8_t*)c->stage_out.p;                                       // the packed container, assembled on the device slice by slice
-    uint8_t* d_index = with_index ? d_out + index_base(nc) : nullptr;
     uint8_t* ws = (uint8_t*)c->work.p;
-    uint32_t* d_err = reinterpret_cast<uint32_t*>(ws + p.off_err);
-    uint64_t* d_sizes = reinterpret_cast<uint64_t*>(ws + p.off_sizes);
-    uint64_t* d_offsets = reinterpret_cast<uint64_t*>(ws + p.off_offsets);
-    uint64_t* d_carry = d_offsets + nc;                                               // (the extra entry of the offsets array: the running end)
-    uint8_t* d_slots = ws + p.off_slots;
-    uint32_t* d_zmap = zmap_bytes(algo, nc) ? reinterpret_cast<uint32_t*>(ws + p.off_zmap) : nullptr;
-    density_hip_header_t hdr{};
-    hdr.magic = DENSITY_HIP_MAGIC; hdr.algo = (uint8_t)algo; hdr.version = 1; hdr.flags = with_index ? DENSITY_HIP_FLAG_BLOCK_INDEX : 0;
-    hdr.chunk_size = (uint32_t)chunk; hdr.n_chunks = (uint32_t)nc; hdr.total_len = n; hdr.container_len = 0;
+    uint32_t* d_err = p.err(ws);
+    uint64_t* h_ends = reinterpret_cast<uint64_t*>(c->pin_sizes.p);                  // the running end of the container behind every slice, as the device reports it
+    const density_hip_header_t hdr = make_header(algo, chunk, nc, n, with_index ? DENSITY_HIP_FLAG_BLOCK_INDEX : 0);
     hipStream_t s = c->stream;
     e = hipMemsetAsync(d_err, 0, sizeof(uint32_t), s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);                                 // (the kernel streams below do not wait for s)
@@ -186,20 +154,18 @@ size_t encode_container_pipelined(DeviceCtx* c, int algo, const uint8_t* input, 
     // end of its predecessor (write_buffer.rs:29-31's running total: the one sequential step, a scan over a few sizes), its streams are gathered
     // there, and the new running end comes back to the host, which then knows what to bring down.
     for (uint32_t k = 0; k < slices && e == hipSuccess; ++k) {
-        const uint32_t first = k * per, count = first + per <= nc ? per : (uint32_t)(nc - first);
-        const uint64_t in_off = (uint64_t)first * chunk, len = n - in_off < (uint64_t)count * chunk ? n - in_off : (uint64_t)count * chunk;
+        const Slice sl = slice_of(k, per, nc, chunk, n);
+        const bool is_last = k + 1 == slices;
         hipEvent_t ev_up = c->pipe_events[3 * k], ev_lay = c->pipe_events[3 * k + 1], ev_enc = c->pipe_events[3 * k + 2];
         hipStream_t ks = c->kern[k & 3u];
-        e = hipMemcpyAsync(d_in + in_off, input + in_off, len, hipMemcpyHostToDevice, c->up);
+        e = hipMemcpyAsync(d_in + sl.off, input + sl.off, sl.len, hipMemcpyHostToDevice, c->up);
         if (e == hipSuccess) e = hipEventRecord(ev_up, c->up);
         if (e == hipSuccess) e = hipStreamWaitEvent(ks, ev_up, 0);
-        if (e == hipSuccess) e = codec_encode(algo, d_in + in_off, len, chunk, count, d_slots + (uint64_t)first * p.stride, p.stride, d_sizes + first,
-                                              d_index ? d_index + in_off / 256 : nullptr, nullptr, d_zmap ? d_zmap + (uint64_t)first * kZmapWordsPerChunk : nullptr, nullptr, d_err, ks);
-        if (e == hipSuccess && k) e = hipStreamWaitEvent(ks, c->pipe_events[3 * (k - 1) + 1], 0);   // the predecessor's running end
-        if (e == hipSuccess) e = launch_layout_encode_batch(d_sizes, first, count, k == 0, k + 1 == slices, hdr, pbase, d_out, bound, d_offsets, d_carry, d_err, ks);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->pin_sizes + k, d_carry, 8, hipMemcpyDeviceToHost, ks);
+        hipEvent_t ev_pred = k ? c->pipe_events[3 * (k - 1) + 1] : nullptr;       // the predecessor's running end
+        if (e == hipSuccess) e = encode_slice(p, ws, d_in, sl, k == 0, is_last, hdr, d_out, bound, ks, nullptr, ev_pred);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_ends + k, p.carry(ws), 8, hipMemcpyDeviceToHost, ks);
         if (e == hipSuccess) e = hipEventRecord(ev_lay, ks);
-        if (e == hipSuccess) e = launch_compact(d_slots + (uint64_t)first * p.stride, p.stride, d_sizes + first, d_offsets + first, count, d_out, d_err, ks, k + 1 < slices);
+        if (e == hipSuccess) e = gather_slice(p, ws, sl, is_last, d_out, ks);
         if (e == hipSuccess) e = hipEventRecord(ev_enc, ks);
     }
     uint64_t begin = pbase, end = pbase;
@@ -207,7 +173,7 @@ size_t encode_container_pipelined(DeviceCtx* c, int algo, const uint8_t* input, 
     for (uint32_t k = 0; k < slices && e == hipSuccess && !too_small; ++k) {
         e = hipEventSynchronize(c->pipe_events[3 * k + 2]);
         if (e != hipSuccess) break;
-        end = c->pin_sizes[k];
+        end = h_ends[k];
         if (end > cap || end > bound || end < begin) { too_small = true; break; }
         e = hipMemcpyAsync(output + begin, d_out + begin, end - begin, hipMemcpyDeviceToHost, c->down);
         begin = align_up(end, 16);
@@ -216,14 +182,11 @@ size_t encode_container_pipelined(DeviceCtx* c, int algo, const uint8_t* input, 
             std::memset(output + end, 0, begin - end);                                // the gap behind a slice's last stream (the gather zeroes those inside a slice)
         }
     }
-    const hipError_t e1 = hipStreamSynchronize(c->up);
-    hipError_t e4 = hipSuccess;
-    for (int i = 0; i < 4; ++i) { const hipError_t x = hipStreamSynchronize(c->kern[i]); if (x != hipSuccess) e4 = x; }
+    e = drain(e, {c->up, c->kern[0], c->kern[1], c->kern[2], c->kern[3]});
     if (e == hipSuccess && !too_small) e = hipMemcpyAsync(output, d_out, pbase, hipMemcpyDeviceToHost, c->down);   // header (written with the last slice), size table, block index
-    const hipError_t e3 = hipStreamSynchronize(c->down);
-    if (e == hipSuccess) e = e1 != hipSuccess ? e1 : e4 != hipSuccess ? e4 : e3;
+    e = drain(e, {c->down});
     uint32_t h_err = 0;
-    if (e == hipSuccess) e = hipMemcpy(&h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = read_back(s, d_err, &h_err);
     if (e != hipSuccess) { set_error("encode (pipelined host path)", e); return 0; }
     if (h_err & 16u) { set_error("encode: device-side watchdog"); return 0; }
     if (h_err || too_small) { set_error("output buffer too small"); return 0; }
@@ -241,8 +204,7 @@ extern "C" {
 
 size_t density_hip_encode(int algo, const uint8_t* input, size_t input_size, uint8_t* output, size_t output_size, size_t chunk_size) {
     g_last_error.clear();
-    chunk_size = normalise_chunk(chunk_size, input_size, algo);
-    if (!valid_algo(algo) || !valid_chunk(chunk_size) || (!input && input_size) || !output) { set_error("bad argument"); return 0; }
+    if (!take_geometry(algo, input_size, &chunk_size) || (!input && input_size) || !output) { set_error("bad argument"); return 0; }
     DeviceCtx* c = acquire_ctx();
     if (!c) return 0;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -252,9 +214,7 @@ size_t density_hip_encode(int algo, const uint8_t* input, size_t input_size, uin
         if (handled) return r;
     }
     const size_t bound = container_bound(algo, input_size, chunk_size);
-    hipError_t e = c->stage_in.ensure(input_size ? input_size : 1);
-    if (e == hipSuccess) e = c->stage_out.ensure(bound);
-    if (e == hipSuccess) e = c->work.ensure(plan_encode(algo, input_size, chunk_size).total);
+    hipError_t e = ensure_staging(c, input_size ? input_size : 1, bound, plan_encode(algo, input_size, chunk_size).total);
     if (e == hipSuccess && input_size) e = copy_host_side_pinned(c->stage_in.p, input, input_size, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) { set_error("staging (H2D)", e); return 0; }
     density_hip_header_t h;
@@ -288,9 +248,7 @@ size_t density_hip_decode(const uint8_t* container, size_t container_size, uint8
         const size_t r = decode_container_pipelined(c, container, h, output, &handled);
         if (handled) return r;
     }
-    hipError_t e = c->stage_in.ensure(h.container_len);
-    if (e == hipSuccess) e = c->stage_out.ensure(h.total_len);
-    if (e == hipSuccess) e = c->work.ensure(plan_decode(h.algo, h.n_chunks, h.chunk_size).total_with_passes);
+    hipError_t e = ensure_staging(c, h.container_len, h.total_len, plan_decode(h.algo, h.n_chunks, h.chunk_size).total_with_passes);
     if (e == hipSuccess) e = copy_host_side_pinned(c->stage_in.p, container, h.container_len, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) { set_error("staging (H2D)", e); return 0; }
     size_t produced = 0;

@@ -1,12 +1,15 @@
-// api_internal.hpp — what the three units of the C ABI share (api.hip: per-device context, plans, the container's device-side drivers and
-// entry points; api_stream.hip: ONE reference stream — the reference's nine symbols, the parallel segments of long Chameleon streams;
-// api_host.hip: the host-pointer container calls, staged or pipelined in slices).  Internal to libdensity_hip.so.
+// api_internal.hpp — what the three units of the C ABI share.  api.hip: per-device context, workspace plans, the container's device-side
+// drivers, the device-pointer and bookkeeping entry points.  api_stream.hip: ONE reference stream — the reference's nine symbols and their
+// device-pointer forms, long Chameleon streams in parallel segments, staged or pipelined from host pointers.  api_host.hip: the host-pointer
+// container calls, staged or pipelined in slices.  Here: geometry of the formats, the context, the kernel-variant bits, the workspace plans with
+// their typed views, and the steps every driver repeats (workspace resolution, read-back, drain, slice arithmetic).  Internal to libdensity_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -27,6 +30,15 @@ extern int g_variant;                 // density_hip_set_kernel_variant
 extern uint64_t g_pass_decodes;       // density_hip_decode_pass_count: Cheetah decodes served by the decode passes
 extern uint64_t g_stream_stats[4];    // density_hip_stream_stats: long streams encoded in segments | encode passes | decoded in segments | long streams decoded sequentially
 void set_error(const char* what, hipError_t e = hipSuccess);
+
+// the bits of density_hip_set_kernel_variant, a test hook: include/density_hip.h says what each one selects (payload bytes are identical in every variant)
+enum Variant : int {
+    kVarSimple = 1, kVarNoIndex = 2, kVarRolePipeline = 4, kVarBatchedStitch = 8, kVarLaneCodec = 16, kVarWaveCodec = 32, kVarStageAudit = 64, kVarSerialDecode = 128,
+    kVarPipeAlways = 256, kVarPipeNever = 512, kVarSerialParse = 1024, kVarRotorOtherSplit = 2048, kVarChainWalk = 4096, kVarWalk64 = 8192, kVarWalk128 = 16384,
+    kVarLionOneWave = 32768,
+    kVarNoRotor = kVarSimple | kVarRolePipeline,   // either way the wave-rotation kernels, and with them segments and pages, are out
+};
+inline bool variant(int bits) { return (g_variant & bits) != 0; }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -71,11 +83,13 @@ inline size_t auto_chunk(size_t n, int algo = DENSITY_HIP_CHAMELEON) {
 }
 inline size_t normalise_chunk(size_t chunk, size_t n, int algo = DENSITY_HIP_CHAMELEON) { return chunk == 0 ? auto_chunk(n, algo) : chunk; }
 inline bool valid_chunk(size_t chunk) { return chunk >= 256 && chunk % 256 == 0 && chunk <= kMaxChunk; }
+// a call's algorithm and chunk size (0 = automatic: *chunk becomes what it stands for) are ones the library takes
+inline bool take_geometry(int algo, size_t n, size_t* chunk) { *chunk = normalise_chunk(*chunk, n, algo); return valid_algo(algo) && valid_chunk(*chunk); }
 inline size_t chunk_count(size_t n, size_t chunk) { return (n + chunk - 1) / chunk; }
 inline size_t index_base(size_t n_chunks) { return align_up(sizeof(density_hip_header_t) + 4 * n_chunks, 16); }
 inline size_t index_bytes(size_t total_len, bool with_index) { return with_index ? (total_len + 255) / 256 : 0; }
 inline size_t payload_base(size_t n_chunks, size_t total_len, bool with_index) { return align_up(index_base(n_chunks) + index_bytes(total_len, with_index), 16); }
-inline bool want_index(int algo) { return algo == DENSITY_HIP_CHAMELEON && !(g_variant & 2); }
+inline bool want_index(int algo) { return algo == DENSITY_HIP_CHAMELEON && !variant(kVarNoIndex); }
 // paged container (DENSITY_HIP_FLAG_PAGED): behind the block index the page directory (per chunk: 16 bytes {n_pages}, then 16 bytes per page), then,
 // on the next page-size boundary of the container, the pages
 inline size_t paged_dir_base(size_t n_chunks, size_t total_len) { return payload_base(n_chunks, total_len, true); }
@@ -107,6 +121,21 @@ struct Buffer {
     }
 };
 
+// pinned host memory of the context (the device's copies to and from it are asynchronous); grows like Buffer
+struct PinnedBuffer {
+    uint8_t* p = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t n) {
+        if (n <= cap) return hipSuccess;
+        release();
+        const size_t want = align_up(n + n / 2, 4096);
+        const hipError_t e = hipHostMalloc((void**)&p, want, hipHostMallocDefault);
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+};
+
 struct DeviceCtx {
     std::mutex mu;
     bool ready = false, selftest_ok = false;
@@ -117,10 +146,8 @@ struct DeviceCtx {
     // the pipelined host-pointer container calls: an upload, a download and four kernel streams, events per slice, the slice sizes in pinned memory
     hipStream_t up = nullptr, down = nullptr, kern[4] = {};
     std::vector<hipEvent_t> pipe_events;
-    uint64_t* pin_sizes = nullptr;
-    size_t pin_sizes_cap = 0;
-    uint8_t* pin_meta = nullptr;             // the pipelined stream calls: per segment sizes, offsets, states as the device reports them
-    size_t pin_meta_cap = 0;
+    PinnedBuffer pin_sizes;                  // the pipelined container encode: the running end of the container behind every slice
+    PinnedBuffer pin_meta;                   // the pipelined stream calls: per segment sizes, offsets, states as the device reports them
     // profiling: event marks accumulated since the last density_hip_last_timings() (name == nullptr opens a call)
     std::vector<hipEvent_t> events;
     std::vector<const char*> names;
@@ -189,20 +216,52 @@ struct PinnedInPlace {
 inline hipError_t copy_host_side_pinned(void* dst, const void* src, size_t n, hipMemcpyKind kind, hipStream_t s) {
     if (n == 0) return hipSuccess;
     const void* host = kind == hipMemcpyHostToDevice ? src : dst;
-    if (n >= (1u << 20) && !debug_env("DENSITY_HIP_RAW_STAGED")) {      // (the switch — debug builds only — is the round-4 fault's reproducer, tools/gpu_host_stream_sequence.py)
-        PinnedInPlace pin(host, n);
-        if (pin) {
-            const hipError_t e = hipMemcpyAsync(dst, src, n, kind, s), e2 = hipStreamSynchronize(s);
-            return e != hipSuccess ? e : e2;
-        }
-    }
+    // (the switch — debug builds only — is the round-4 fault's reproducer, tools/gpu_host_stream_sequence.py; a pin that fails leaves the copy pageable)
+    const bool pin_it = n >= (1u << 20) && !debug_env("DENSITY_HIP_RAW_STAGED");
+    PinnedInPlace pin(pin_it ? host : nullptr, n);
     const hipError_t e = hipMemcpyAsync(dst, src, n, kind, s), e2 = hipStreamSynchronize(s);
     return e != hipSuccess ? e : e2;
 }
 constexpr uint32_t kPipeMaxSlices = 48;
 // the upload, download and kernel streams of the pipelined host-pointer calls and n_events events (api_host.hip)
 bool pipe_streams(DeviceCtx* c, uint32_t n_events);
-hipError_t pin_meta_ensure(DeviceCtx* c, size_t bytes);
+// The workspace of a device-pointer call: the caller's if it gave one — it must hold `need` — else the context's, grown to `own` (the container decode
+// asks for the decode passes' scratch on top of `need`).  *ws_size, where wanted: what the workspace holds.
+inline int resolve_workspace(DeviceCtx* c, void* d_workspace, size_t workspace_size, size_t need, size_t own, uint8_t** ws, size_t* ws_size = nullptr) {
+    if (d_workspace && workspace_size < need) { set_error("workspace too small"); return DENSITY_HIP_ERR_CAPACITY; }
+    const hipError_t e = d_workspace ? hipSuccess : c->work.ensure(own);
+    if (e != hipSuccess) { set_error("workspace allocation", e); return DENSITY_HIP_ERR_RUNTIME; }
+    *ws = (uint8_t*)(d_workspace ? d_workspace : c->work.p);
+    if (ws_size) *ws_size = d_workspace ? workspace_size : c->work.cap;
+    return DENSITY_HIP_OK;
+}
+// the staging buffers of a host-pointer call: its input and its output on the device, the context's workspace
+inline hipError_t ensure_staging(DeviceCtx* c, size_t in_bytes, size_t out_bytes, size_t ws_bytes) {
+    hipError_t e = c->stage_in.ensure(in_bytes);
+    if (e == hipSuccess) e = c->stage_out.ensure(out_bytes);
+    return e == hipSuccess ? c->work.ensure(ws_bytes) : e;
+}
+// The end of a pipelined call: every stream it used is synchronised whatever happened before — nothing may still be reading or writing the caller's
+// buffers when they are unpinned — and the first error wins (`e`: the call's status so far).
+inline hipError_t drain(hipError_t e, std::initializer_list<hipStream_t> streams) {
+    for (hipStream_t q : streams) { const hipError_t x = hipStreamSynchronize(q); if (e == hipSuccess) e = x; }
+    return e;
+}
+// slice k of a pipelined or batched call, `per` chunks to a slice: chunks [first, first + count) and their bytes [off, off + len) of the `total` plain bytes
+struct Slice { uint32_t first, count; uint64_t off, len; };
+inline Slice slice_of(uint32_t k, uint32_t per, size_t n_chunks, size_t chunk, size_t total) {
+    const uint32_t first = k * per, count = first + per <= n_chunks ? per : (uint32_t)(n_chunks - first);
+    const uint64_t off = (uint64_t)first * chunk;
+    return {first, count, off, std::min<uint64_t>(total - off, (uint64_t)count * chunk)};
+}
+// The error word, and with it one more small object (a header, a size), back on the host: queued on s, complete on return.  What the bits of the
+// word mean is the caller's business.
+inline hipError_t read_back(hipStream_t s, const uint32_t* d_err, uint32_t* h_err, void* h_obj = nullptr, const void* d_obj = nullptr, size_t obj_bytes = 0) {
+    hipError_t e = h_obj ? hipMemcpyAsync(h_obj, d_obj, obj_bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpyAsync(h_err, d_err, sizeof(*h_err), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return e;
+}
 
 constexpr size_t kSerialSlots = 16384;   // concurrent chunk streams of the functional Cheetah/Lion kernels (one lane each; 12 / 28 GiB of tables when all are in use)
 constexpr size_t kSerialTableBudget = 8ull << 30;   // ... but never more than 8 GiB of tables (the count comes from an untrusted header on decode): Cheetah 10922 streams, Lion 4681
@@ -217,12 +276,32 @@ inline size_t serial_tables(int algo, size_t n_chunks) { return algo == DENSITY_
 
 inline size_t zmap_bytes(int algo, size_t n_chunks) { return (algo == DENSITY_HIP_CHAMELEON && n_chunks <= kMaxPipelinedChunks) ? align_up((n_chunks ? n_chunks : 1) * kZmapWordsPerChunk * 4, kAlign) : 0; }
 
+// The plans: where everything lies in a workspace (the sizes the ABI reports follow from the offsets), and the workspace `ws` seen through them.
 struct EncodePlan {
     size_t chunk, n_chunks, stride, off_err, off_sizes, off_offsets, off_slots, off_tables, off_zmap, off_stage, total;
-};EncodePlan plan_encode(int algo, size_t n, size_t chunk);
+    uint32_t* err(uint8_t* ws) const { return reinterpret_cast<uint32_t*>(ws + off_err); }
+    uint32_t* page_counter(uint8_t* ws) const { return err(ws) + 4; }                  // (the paged form: pages handed out so far)
+    uint64_t* sizes(uint8_t* ws) const { return reinterpret_cast<uint64_t*>(ws + off_sizes); }
+    uint64_t* offsets(uint8_t* ws) const { return reinterpret_cast<uint64_t*>(ws + off_offsets); }
+    uint64_t* carry(uint8_t* ws) const { return offsets(ws) + n_chunks; }               // (the extra entry of the offsets array: the running end)
+    uint8_t* slots(uint8_t* ws) const { return ws + off_slots; }
+    uint8_t* tables(uint8_t* ws) const { return ws + off_tables; }
+    uint32_t* zmap(uint8_t* ws) const { return off_stage > off_zmap ? reinterpret_cast<uint32_t*>(ws + off_zmap) : nullptr; }   // nullptr: no zmap (zmap_bytes() == 0)
+    uint8_t* stage(uint8_t* ws) const { return total > off_stage ? ws + off_stage : nullptr; }                                 // nullptr: the exchange passes will not run
+};
+EncodePlan plan_encode(int algo, size_t n, size_t chunk);
 struct DecodePlan {
     size_t off_err, off_sizes, off_offsets, off_produced, off_tables, off_zmap, off_pass, total, total_with_passes;
-};// out_stride != 0 (the container's chunk size / a stream's output capacity): Cheetah's decode passes (decode_passes.hip) want a dword and
+    uint32_t* err(uint8_t* ws) const { return reinterpret_cast<uint32_t*>(ws + off_err); }
+    uint64_t* sizes(uint8_t* ws) const { return reinterpret_cast<uint64_t*>(ws + off_sizes); }
+    uint64_t* offsets(uint8_t* ws) const { return reinterpret_cast<uint64_t*>(ws + off_offsets); }
+    uint64_t* produced(uint8_t* ws) const { return reinterpret_cast<uint64_t*>(ws + off_produced); }
+    uint8_t* tables(uint8_t* ws) const { return ws + off_tables; }
+    uint32_t* zmap(uint8_t* ws) const { return total > off_zmap ? reinterpret_cast<uint32_t*>(ws + off_zmap) : nullptr; }       // nullptr: no zmap (zmap_bytes() == 0)
+    // nullptr: no decode passes for this container, or a (caller's smaller) workspace of ws_size bytes that does not hold their scratch: the one-wave decoder
+    uint8_t* pass(uint8_t* ws, size_t ws_size) const { return (ws_size >= total_with_passes && total_with_passes > total) ? ws + off_pass : nullptr; }
+};
+// out_stride != 0 (the container's chunk size / a stream's output capacity): Cheetah's decode passes (decode_passes.hip) want a dword and
 // a half per quad of scratch behind everything else; `total` is what the one-wave decoders need, `total_with_passes` what the passes need
 DecodePlan plan_decode(int algo, size_t n_chunks, size_t out_stride = 0);
 
@@ -238,9 +317,21 @@ size_t container_bound(int algo, size_t n, size_t chunk);
 size_t container_bound_slotted(int algo, size_t n, size_t chunk);
 int check_header(const density_hip_header_t& h, size_t container_size);
 
+// a container's header as the encoders hand it to the layout kernels (container_len: theirs to fill in)
+inline density_hip_header_t make_header(int algo, size_t chunk, size_t n_chunks, size_t total_len, uint32_t flags) {
+    return density_hip_header_t{DENSITY_HIP_MAGIC, (uint8_t)algo, 1, (uint16_t)flags, (uint32_t)chunk, (uint32_t)n_chunks, total_len, 0};
+}
+enum class Form { Packed, Slotted, Paged };   // how a container's chunk streams lie: gathered | in worst-case slots | in pages
+// One slice (slice_of) of a packed container's encode on stream s: its chunks into their worst-case slots, then — behind `predecessor`, the event
+// of the slice in front where that ran on another stream — its place in the container from the running end *p.carry(ws); gather_slice brings the
+// streams there.  The batched device encode and the pipelined host encode are these two per slice.  prof: the marks of the device call.
+hipError_t encode_slice(const EncodePlan& p, uint8_t* ws, const uint8_t* d_in, const Slice& sl, bool is_first, bool is_last, const density_hip_header_t& hdr,
+                        uint8_t* d_out, uint64_t cap, hipStream_t s, Profiler* prof, hipEvent_t predecessor);
+hipError_t gather_slice(const EncodePlan& p, uint8_t* ws, const Slice& sl, bool is_last, uint8_t* d_out, hipStream_t s);
+
 // device-side drivers of the container (api.hip; ctx already acquired; `ws` points at a workspace of sufficient size)
 int run_encode_container(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, size_t chunk,
-                         uint8_t* ws, hipStream_t s, density_hip_header_t* header_out, bool slotted = false, bool paged = false);
+                         uint8_t* ws, hipStream_t s, density_hip_header_t* header_out, Form form = Form::Packed);
 int run_decode_container(DeviceCtx* c, const uint8_t* d_in, size_t container_size, const density_hip_header_t& h, uint8_t* d_out,
                          size_t cap, uint8_t* ws, hipStream_t s, size_t* decoded_out, size_t ws_size = 0);
 // ... of one reference stream (api_stream.hip)

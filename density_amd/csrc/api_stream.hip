@@ -1,6 +1,6 @@
 // api_stream.hip — ONE reference stream (include/density_hip.h section 1: the reference's nine symbols, chameleon.rs:70-83, cheetah.rs:105-118,
 // lion.rs:193-206, and their device-pointer forms): short streams on one work-group / wave, long Chameleon streams encoded and decoded in
-// parallel segments, byte for byte the reference's stream.
+// parallel segments, byte for byte the reference's stream; from host pointers staged whole, long Chameleon streams pipelined in slices.
 #include "api_internal.hpp"
 
 #include <chrono>
@@ -34,6 +34,10 @@ struct SegEncode {
     uint64_t *d_sizes = nullptr, *d_offsets = nullptr, *d_carry = nullptr;       // d_carry: the running end of the stream (the pipelined host call gathers as it goes)
     uint32_t *d_gspec = nullptr, *d_gfinal = nullptr, *d_raw = nullptr, *d_err = nullptr;
     size_t seg_at(size_t k) const { return k == 0 ? 0 : C0 + (k - 1) * C; }       // where segment k starts
+    // What makes a segment's successor final: the successor speculated on a start image that is the truth exactly when the segment coded all its
+    // blocks (no raw copy: it wrote every one of its quads) and ended calm.  So with segment a started from the truth, k > a + 1 is final iff this
+    // holds for every segment a + 1 .. k - 1 (raw, gfinal: what segment k - 1 reported).
+    static bool hands_on_truth(uint32_t raw, uint32_t gfinal) { return raw == 0 && (gfinal & 0x7fffffffu) == 0; }
     size_t seg_len(size_t k) const { const size_t left = n - seg_at(k), len = k == 0 ? C0 : C; return left < len ? left : len; }
     // the first segment runs alone, ahead of everything else: a quarter of the others' length (whole rounds)
     hipError_t setup(DeviceCtx* c, size_t n_, hipStream_t s) {
@@ -57,14 +61,21 @@ struct SegEncode {
         if (e == hipSuccess) e = hipMemcpyAsync(d_gspec, calm.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, s);   // (pageable: copied before the call returns)
         return e;
     }
+    // last writers of the inner segments (every segment but the stream's first and last; whole rounds: only the last can be short) among [a, b)
+    hipError_t lastwriters(const uint8_t* d_in, size_t a, size_t b, hipStream_t s) const {
+        a = std::max<size_t>(a, 1); b = std::min(b, S - 1);
+        return b > a ? launch_rotor_lastwriters(d_in + seg_at(a), C, (uint32_t)(b - a), d_lw + a * kSegImageBytes, d_err, s) : hipSuccess;
+    }
+    SegArgs reports(size_t k) const {                                              // where segment k (and its successors) leave final image, state and raw-copy blocks
+        SegArgs r;
+        r.final_images = d_final + k * kSegImageBytes; r.final_guard = d_gfinal + k; r.raw_blocks = d_raw + k;
+        return r;
+    }
     // segments [a, a + count) from their start images (d_start) and start states (d_gspec), reporting final images, states and raw-copy blocks
     hipError_t speculate(const uint8_t* d_in, size_t a, size_t count, hipStream_t s) const {
-        SegArgs b;
+        SegArgs b = reports(a);
         b.init_images = d_start + a * kSegImageBytes;
         b.init_guard = d_gspec + a;
-        b.final_images = d_final + a * kSegImageBytes;
-        b.final_guard = d_gfinal + a;
-        b.raw_blocks = d_raw + a;
         const size_t left = n - seg_at(a);
         return launch_rotor_encode_seg(d_in + seg_at(a), left < count * C ? left : count * C, C, (uint32_t)count, d_stage + a * stride, stride, d_sizes + a, d_err, b, s);
     }
@@ -80,16 +91,20 @@ hipError_t seg_encode_passes(const SegEncode& L, const uint8_t* d_in, size_t fir
     hipError_t e = hipSuccess;
     size_t advanced = S;                                                           // segments the previous pass made final
     const size_t first_in = first;
+    // the sizes of slots first_in .. upto - 1 and the error word as they stand, complete on return
+    const auto report = [&](size_t upto) {
+        hipError_t x = hipMemcpyAsync(h_sizes.data() + first_in, L.d_sizes + first_in, (upto - first_in) * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+        if (x == hipSuccess && h_err) x = hipMemcpyAsync(h_err, L.d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+        if (x == hipSuccess) x = hipStreamSynchronize(s);
+        return x;
+    };
     for (int pass = 0; e == hipSuccess && first < S; ++pass) {
         // (a pass that gets nowhere — raw copies all over — is not repeated for long: the remainder then runs as one chunk)
         const bool rest_as_one = pass >= 16 || (pass >= 3 && advanced < 8);
         // segment `first` (or, after too many passes, everything that is left as one chunk) from its exact start
-        SegArgs a;
+        SegArgs a = L.reports(first);
         a.init_images = first ? L.d_final + (first - 1) * img : nullptr;
         a.init_guard = first ? L.d_gfinal + (first - 1) : nullptr;
-        a.final_images = L.d_final + first * img;
-        a.final_guard = L.d_gfinal + first;
-        a.raw_blocks = L.d_raw + first;
         const size_t left = L.n - L.seg_at(first), len1 = first == 0 ? L.C0 : L.C;
         e = hipMemsetAsync(L.d_raw + first, 0, sizeof(uint32_t), s);
         if (e == hipSuccess)
@@ -104,16 +119,14 @@ hipError_t seg_encode_passes(const SegEncode& L, const uint8_t* d_in, size_t fir
         if (e == hipSuccess) e = L.speculate(d_in, first + 1, rest, s);
         if (e == hipSuccess) e = hipMemcpyAsync(h_gfinal.data(), L.d_gfinal, S * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(h_raw.data(), L.d_raw, S * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-        // (with the report: the sizes of every slot and the error word as they stand — if this pass turns out to be the last one they are final, and the
+        // (with the verdicts: the sizes of every slot and the error word as they stand — if this pass turns out to be the last one they are final, and the
         // call saves two host round trips: round 5)
-        if (e == hipSuccess) e = hipMemcpyAsync(h_sizes.data() + first_in, L.d_sizes + first_in, (S - first_in) * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && h_err) e = hipMemcpyAsync(h_err, L.d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e == hipSuccess) e = report(S);
         if (e != hipSuccess) break;
         sizes_are_current = true;
-        // segment first+1 started from the truth; k >= first+2 is final iff every segment first+1 .. k-1 coded all its blocks and k-1 ended calm
+        // segment first+1 started from the truth; k >= first+2 is final iff every segment first+1 .. k-1 handed on the truth
         size_t k = first + 2;
-        while (k < S && h_raw[k - 1] == 0 && (h_gfinal[k - 1] & 0x7fffffffu) == 0) ++k;
+        while (k < S && SegEncode::hands_on_truth(h_raw[k - 1], h_gfinal[k - 1])) ++k;
         if (trace) fprintf(stderr, "[density_hip prof] segmented stream encode: pass %d, %zu segments of %zu bytes, final up to segment %zu\n", pass, S, L.C, k);
         advanced = k - first;
         first = k;                                                                // (== S: done)
@@ -124,10 +137,7 @@ hipError_t seg_encode_passes(const SegEncode& L, const uint8_t* d_in, size_t fir
     // passes that ran out at `first` < S: slots first .. are ONE stream in slot `first`
     *used = first < S ? first + 1 : S;
     if (sizes_are_current) return hipSuccess;                                      // the last pass's report carried them (and the error word)
-    e = hipMemcpyAsync(h_sizes.data() + first_in, L.d_sizes + first_in, (*used - first_in) * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && h_err) e = hipMemcpyAsync(h_err, L.d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return e;
+    return report(*used);
 }
 
 int run_stream_encode_segmented(DeviceCtx* c, const uint8_t* d_in, size_t n, uint8_t* d_out, hipStream_t s, size_t* size_out) {
@@ -137,11 +147,10 @@ int run_stream_encode_segmented(DeviceCtx* c, const uint8_t* d_in, size_t n, uin
     if (e != hipSuccess) { set_error("workspace allocation (segmented stream encode)", e); return DENSITY_HIP_ERR_RUNTIME; }
     const size_t S = L.S;
     std::vector<uint64_t> h_sizes(S), h_offsets(S);
-    // last writers of every segment that has a successor and a predecessor (whole rounds: only the last segment can be short)
-    // (on the context's second stream, beside the first segment's encode; joined before the first merge)
+    // the last writers on the context's second stream, beside the first segment's encode; joined before the first merge
     e = hipEventRecord(c->batch_done[0], s);
     if (e == hipSuccess) e = hipStreamWaitEvent(c->stitch_stream, c->batch_done[0], 0);
-    if (e == hipSuccess && S > 2) e = launch_rotor_lastwriters(d_in + L.C0, L.C, (uint32_t)(S - 2), L.d_lw + kSegImageBytes, L.d_err, c->stitch_stream);
+    if (e == hipSuccess) e = L.lastwriters(d_in, 0, S, c->stitch_stream);
     if (e == hipSuccess) e = hipEventRecord(c->stitch_done, c->stitch_stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(s, c->stitch_done, 0);
     size_t used = S;
@@ -165,16 +174,17 @@ int run_stream_encode_segmented(DeviceCtx* c, const uint8_t* d_in, size_t n, uin
 int run_stream_encode(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, uint8_t* ws, hipStream_t s,
                       size_t* size_out) {
     if (cap < safe_size(algo, n)) { set_error("output capacity below safe_encode_buffer_size()"); return DENSITY_HIP_ERR_CAPACITY; }
-    if (algo == DENSITY_HIP_CHAMELEON && n >= kSegMinStream && n < (64ull << 30) && (reinterpret_cast<uintptr_t>(d_in) & 3) == 0 && !(g_variant & 5) && !g_rotor_unsafe) {   // (segments are at most 4 MiB: 32-bit positions inside them; 64 GiB = 16384 segments)
+    if (algo == DENSITY_HIP_CHAMELEON && n >= kSegMinStream && n < (64ull << 30) && (reinterpret_cast<uintptr_t>(d_in) & 3) == 0 && !variant(kVarNoRotor) && !g_rotor_unsafe) {
+        // (segments are at most 4 MiB: 32-bit positions inside them; 64 GiB = 16384 segments)
         *size_out = 0;
         return run_stream_encode_segmented(c, d_in, n, d_out, s, size_out);
     }
-    uint64_t* d_sizes = reinterpret_cast<uint64_t*>(ws + kAlign);
     *size_out = 0;
     if (n == 0) return DENSITY_HIP_OK;
     Profiler prof(c, s);
     const DecodePlan sp = plan_decode(algo, 1);   // stream calls share the one-chunk decode layout
-    uint32_t* d_err = reinterpret_cast<uint32_t*>(ws + sp.off_err);
+    uint32_t* d_err = sp.err(ws);
+    uint64_t* d_sizes = sp.sizes(ws);
     hipError_t e = hipMemsetAsync(d_err, 0, sizeof(uint32_t), s);
     // a long Cheetah / Lion stream is ONE chunk for the exchange passes (exchange_stages.hip): their scratch comes from the context
     uint8_t* d_stage = nullptr;
@@ -182,13 +192,11 @@ int run_stream_encode(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, uin
         e = c->seg.ensure(stage_scratch_bytes(algo, n, 1) + kAlign);
         d_stage = (uint8_t*)c->seg.p;
     }
-    if (e == hipSuccess) e = codec_encode(algo, d_in, n, n, 1, d_out, 0, d_sizes, nullptr, ws + sp.off_tables, zmap_bytes(algo, 1) ? reinterpret_cast<uint32_t*>(ws + sp.off_zmap) : nullptr, d_stage, d_err, s);
+    if (e == hipSuccess) e = codec_encode(algo, d_in, n, n, 1, d_out, 0, d_sizes, nullptr, sp.tables(ws), sp.zmap(ws), d_stage, d_err, s);
     prof.mark(encode_kernel_name(algo));
     uint64_t h_size = 0;
     uint32_t h_err = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_size, d_sizes, sizeof(h_size), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = read_back(s, d_err, &h_err, &h_size, d_sizes, sizeof(h_size));
     if (e != hipSuccess) { set_error("stream encode", e); return DENSITY_HIP_ERR_RUNTIME; }
     if (h_err) { set_error("stream encode: device-side watchdog"); return DENSITY_HIP_ERR_RUNTIME; }
     *size_out = (size_t)h_size;
@@ -245,6 +253,26 @@ struct SegDecode {
         d_err = d_info + 16;                                                      // [0] the real pass, [1] the last-writer pass (ignored)
         return true;
     }
+    // Segments [first, first + count) — laid out in d_offsets / d_sizes, whole on the device — decoded on stream q into d_out, the range's place in the
+    // output with out_total bytes of room: last writers from empty dictionaries, start images laid over `base_image` (the dictionary in front of the
+    // range), the real pass.  carry_on: one image more, the one the NEXT range starts from, is made and kept in d_carry.
+    hipError_t decode_range(const uint8_t* d_in, size_t first, size_t count, uint8_t* d_out, uint64_t out_total, const uint8_t* base_image, bool carry_on, hipStream_t q) const {
+        const size_t img = kSegImageBytes;
+        const auto pass = [&](uint32_t* err, const SegArgs& a) {
+            return launch_rotor_decode_seg(d_in, d_offsets + first, d_sizes + first, (uint32_t)count, d_out, kChunkBytes, out_total, d_index + first * kChunkBlocks,
+                                           d_zmap + first * kZmapWordsPerChunk, d_produced + first, err, a, q);
+        };
+        SegArgs lw;
+        lw.final_images = d_lw + first * img;
+        lw.lastwriters_only = 1;
+        hipError_t e = pass(d_err + 1, lw);
+        if (e == hipSuccess) e = launch_merge_images(base_image, d_lw + first * img, d_start + first * img, (uint32_t)count + (carry_on ? 1 : 0), q);
+        if (e == hipSuccess && carry_on) e = hipMemcpyAsync(d_carry, d_start + (first + count) * img, img, hipMemcpyDeviceToDevice, q);
+        SegArgs real;
+        real.init_images = d_start + first * img;
+        if (e == hipSuccess) e = pass(d_err, real);
+        return e;
+    }
 };
 
 int run_stream_decode_segmented(DeviceCtx* c, const uint8_t* d_in, size_t E, uint8_t* d_out, size_t cap, hipStream_t s, size_t* size_out, bool* handled) {
@@ -255,29 +283,24 @@ int run_stream_decode_segmented(DeviceCtx* c, const uint8_t* d_in, size_t E, uin
         if (e != hipSuccess) { set_error("workspace allocation (segmented stream decode)", e); return DENSITY_HIP_ERR_RUNTIME; }
         return DENSITY_HIP_OK;
     }
-    const uint32_t kChunkBlocks = D.kChunkBlocks;
-    const size_t kChunkBytes = D.kChunkBytes, max_chunks = D.max_chunks, index_bytes = D.index_bytes, img = kSegImageBytes;
-    uint8_t *base = D.base, *d_index = D.d_index;
-    uint32_t *d_pos32 = D.d_pos32, *d_info = D.d_info, *d_err = D.d_err;
-    uint64_t *d_chunk_offset = D.d_chunk_offset, *d_offsets = D.d_offsets, *d_sizes = D.d_sizes, *d_produced = D.d_produced;
     const bool trace = debug_env("DENSITY_HIP_PROF") != nullptr;
-    e = hipMemsetAsync(d_chunk_offset, 0, (max_chunks + 2) * sizeof(uint64_t), s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_info, 0, 18 * sizeof(uint32_t), s);
+    e = hipMemsetAsync(D.d_chunk_offset, 0, (D.max_chunks + 2) * sizeof(uint64_t), s);
+    if (e == hipSuccess) e = hipMemsetAsync(D.d_info, 0, 18 * sizeof(uint32_t), s);
     // Parse.  A pair of incompressible records behind the head means raw copies follow: the parse is final up to that pair, the head walk
     // (real FSM) starts over from it and takes the raw copies, the parallel parse resumes behind them — up to 16 such episodes.
     uint32_t info[8] = {};
     uint32_t from_block = 0;
     uint64_t from_pos = 0;
     bool parsed = false;
-    std::vector<uint64_t> h_off(max_chunks + 2), h_offsets, h_sizes;
+    std::vector<uint64_t> h_off(D.max_chunks + 2), h_offsets, h_sizes;
     for (int episode = 0; e == hipSuccess && episode < 16; ++episode) {
         // ONE host round trip per episode (round 5; there were three): the start words go up in front of the parse on the same stream — they live
         // on this frame until the synchronisation below —, the verdict and the chunk offsets come down together behind it
         const uint32_t start[3] = {from_block, (uint32_t)from_pos, (uint32_t)(from_pos >> 32)};
-        e = hipMemcpyAsync(d_info + 8, start, sizeof(start), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = launch_stream_parse(d_in, E, from_pos, base, d_index, max_chunks * kChunkBlocks, d_chunk_offset, kChunkBlocks, d_pos32, d_info, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(info, d_info, sizeof(info), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_off.data(), d_chunk_offset, (max_chunks + 2) * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+        e = hipMemcpyAsync(D.d_info + 8, start, sizeof(start), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = launch_stream_parse(d_in, E, from_pos, D.base, D.d_index, D.max_chunks * D.kChunkBlocks, D.d_chunk_offset, D.kChunkBlocks, D.d_pos32, D.d_info, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(info, D.d_info, sizeof(info), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_off.data(), D.d_chunk_offset, (D.max_chunks + 2) * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) break;
         if (trace) fprintf(stderr, "[density_hip prof] segmented stream decode: parse from block %u: status %u, head to block %u, %u whole blocks, first incompressible pair at %d\n",
@@ -286,24 +309,30 @@ int run_stream_decode_segmented(DeviceCtx* c, const uint8_t* d_in, size_t E, uin
         if (info[7] == 0xffffffffu) { parsed = true; break; }
         if (info[7] < from_block) break;                                          // (cannot happen)
         uint32_t p32 = 0;
-        e = hipMemcpyAsync(&p32, d_pos32 + info[7], sizeof(p32), hipMemcpyDeviceToHost, s);
+        e = hipMemcpyAsync(&p32, D.d_pos32 + info[7], sizeof(p32), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         from_block = info[7]; from_pos = p32;
     }
     if (e != hipSuccess) { set_error("segmented stream decode (parse)", e); return DENSITY_HIP_ERR_RUNTIME; }
     const uint64_t whole = info[4], end_pos = ((uint64_t)info[6] << 32) | info[5];
-    if (!parsed || whole < 2 * kChunkBlocks || end_pos > E) { if (trace) fprintf(stderr, "[density_hip prof]   -> sequential path (not calm enough / short)\n"); return DENSITY_HIP_OK; }
+    if (!parsed || whole < 2 * D.kChunkBlocks || end_pos > E) { if (trace) fprintf(stderr, "[density_hip prof]   -> sequential path (not calm enough / short)\n"); return DENSITY_HIP_OK; }
     // `whole` comes from the (untrusted) stream, the index was sized from the OUTPUT capacity: a stream that holds more blocks than the
     // output has room for is the sequential path's to refuse (a format error), before anything is sized or filled with it
-    if (whole > max_chunks * kChunkBlocks || whole > index_bytes) { if (trace) fprintf(stderr, "[density_hip prof]   -> sequential path (stream longer than the output: %llu blocks)\n", (unsigned long long)whole); return DENSITY_HIP_OK; }
+    if (whole > D.max_chunks * D.kChunkBlocks || whole > D.index_bytes) {
+        if (trace) fprintf(stderr, "[density_hip prof]   -> sequential path (stream longer than the output: %llu blocks)\n", (unsigned long long)whole);
+        return DENSITY_HIP_OK;
+    }
     // beyond the whole blocks the index says "ragged" = stop (an episode that was started over may have written further); in stream order in front of
     // the decode passes, no round trip
-    e = hipMemsetAsync(d_index + whole, 0x7f, index_bytes - whole, s);
+    e = hipMemsetAsync(D.d_index + whole, 0x7f, D.index_bytes - whole, s);
     if (e != hipSuccess) { set_error("segmented stream decode (parse)", e); return DENSITY_HIP_ERR_RUNTIME; }
     const bool ragged = end_pos < E;
-    const size_t n_chunks = (whole + (ragged ? 1 : 0) + kChunkBlocks - 1) / kChunkBlocks;
-    if (n_chunks > max_chunks || (n_chunks - 1) * kChunkBytes >= cap) { if (trace) fprintf(stderr, "[density_hip prof]   -> sequential path (capacity: %zu chunks, cap %zu)\n", n_chunks, cap); return DENSITY_HIP_OK; }
-    if (ragged && whole % kChunkBlocks == 0) h_off[whole / kChunkBlocks] = end_pos;   // a ragged end that opens a chunk of its own
+    const size_t n_chunks = (whole + (ragged ? 1 : 0) + D.kChunkBlocks - 1) / D.kChunkBlocks;
+    if (n_chunks > D.max_chunks || (n_chunks - 1) * D.kChunkBytes >= cap) {
+        if (trace) fprintf(stderr, "[density_hip prof]   -> sequential path (capacity: %zu chunks, cap %zu)\n", n_chunks, cap);
+        return DENSITY_HIP_OK;
+    }
+    if (ragged && whole % D.kChunkBlocks == 0) h_off[whole / D.kChunkBlocks] = end_pos;   // a ragged end that opens a chunk of its own
     h_off[0] = 0;
     h_offsets.resize(n_chunks); h_sizes.resize(n_chunks);
     for (size_t k = 0; k < n_chunks; ++k) {
@@ -311,31 +340,24 @@ int run_stream_decode_segmented(DeviceCtx* c, const uint8_t* d_in, size_t E, uin
         h_sizes[k] = (k + 1 < n_chunks ? h_off[k + 1] : (uint64_t)E) - h_off[k];
         if (k && h_off[k] <= h_off[k - 1]) return DENSITY_HIP_OK;                     // (cannot happen; never hand the kernels a broken layout)
     }
-    const uint64_t out_total = cap < n_chunks * kChunkBytes ? cap : n_chunks * kChunkBytes;
-    uint32_t* d_zmap = D.d_zmap;
-    if (!rotor_decode_eligible(d_out, (uint32_t)n_chunks, kChunkBytes, out_total, d_index, d_zmap) || g_rotor_unsafe) { if (trace) fprintf(stderr, "[density_hip prof]   -> sequential path (buffers not eligible)\n"); return DENSITY_HIP_OK; }
-    e = hipMemcpyAsync(d_offsets, h_offsets.data(), n_chunks * sizeof(uint64_t), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_sizes, h_sizes.data(), n_chunks * sizeof(uint64_t), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(D.d_zero, 0, img, s);
-    SegArgs lw;
-    lw.final_images = D.d_lw;
-    lw.lastwriters_only = 1;
-    if (e == hipSuccess) e = launch_rotor_decode_seg(d_in, d_offsets, d_sizes, (uint32_t)n_chunks, d_out, kChunkBytes, out_total, d_index, d_zmap, d_produced, d_err + 1, lw, s);
-    if (e == hipSuccess) e = launch_merge_images(D.d_zero, D.d_lw, D.d_start, (uint32_t)n_chunks, s);
-    SegArgs real;
-    real.init_images = D.d_start;
-    if (e == hipSuccess) e = launch_rotor_decode_seg(d_in, d_offsets, d_sizes, (uint32_t)n_chunks, d_out, kChunkBytes, out_total, d_index, d_zmap, d_produced, d_err, real, s);
+    const uint64_t out_total = cap < n_chunks * D.kChunkBytes ? cap : n_chunks * D.kChunkBytes;
+    if (!rotor_decode_eligible(d_out, (uint32_t)n_chunks, D.kChunkBytes, out_total, D.d_index, D.d_zmap) || g_rotor_unsafe) {
+        if (trace) fprintf(stderr, "[density_hip prof]   -> sequential path (buffers not eligible)\n");
+        return DENSITY_HIP_OK;
+    }
+    e = hipMemcpyAsync(D.d_offsets, h_offsets.data(), n_chunks * sizeof(uint64_t), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(D.d_sizes, h_sizes.data(), n_chunks * sizeof(uint64_t), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(D.d_zero, 0, kSegImageBytes, s);      // the dictionary in front of the stream: empty
+    if (e == hipSuccess) e = D.decode_range(d_in, 0, n_chunks, d_out, out_total, D.d_zero, false, s);
     uint64_t h_last = 0;
     uint32_t h_err = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_last, d_produced + (n_chunks - 1), sizeof(h_last), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = read_back(s, D.d_err, &h_err, &h_last, D.d_produced + (n_chunks - 1), sizeof(h_last));
     if (e != hipSuccess) { set_error("segmented stream decode", e); return DENSITY_HIP_ERR_RUNTIME; }
     *handled = true;
     ++g_stream_stats[2];
     if (trace) fprintf(stderr, "[density_hip prof]   -> %zu segments decoded in parallel, err %u\n", n_chunks, h_err);
     if (h_err) { set_error("truncated stream or output too small"); return DENSITY_HIP_ERR_FORMAT; }
-    *size_out = (n_chunks - 1) * kChunkBytes + (size_t)h_last;
+    *size_out = (n_chunks - 1) * D.kChunkBytes + (size_t)h_last;
     return DENSITY_HIP_OK;
 }
 
@@ -345,7 +367,7 @@ int run_stream_decode(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, uin
                       size_t* size_out) {
     *size_out = 0;
     if (n == 0) return DENSITY_HIP_OK;
-    if (algo == DENSITY_HIP_CHAMELEON && n >= kSegDecodeMin && n < (1ull << 32) && !(g_variant & 5) && !g_rotor_unsafe) {   // (the parse keeps 32-bit stream positions)
+    if (algo == DENSITY_HIP_CHAMELEON && n >= kSegDecodeMin && n < (1ull << 32) && !variant(kVarNoRotor) && !g_rotor_unsafe) {   // (the parse keeps 32-bit stream positions)
         bool handled = false;
         const int rc = run_stream_decode_segmented(c, d_in, n, d_out, cap, s, size_out, &handled);
         if (rc != DENSITY_HIP_OK || handled) return rc;
@@ -353,10 +375,8 @@ int run_stream_decode(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, uin
         ++g_stream_stats[3];
     }
     const DecodePlan p = plan_decode(algo, 1);
-    uint32_t* d_err = reinterpret_cast<uint32_t*>(ws + p.off_err);
-    uint64_t* d_sizes = reinterpret_cast<uint64_t*>(ws + p.off_sizes);
-    uint64_t* d_offsets = reinterpret_cast<uint64_t*>(ws + p.off_offsets);
-    uint64_t* d_produced = reinterpret_cast<uint64_t*>(ws + p.off_produced);
+    uint32_t* d_err = p.err(ws);
+    uint64_t *d_sizes = p.sizes(ws), *d_offsets = p.offsets(ws), *d_produced = p.produced(ws);
     const uint64_t h_size = n, h_off = 0;
     Profiler prof(c, s);
     hipError_t e = hipMemsetAsync(d_err, 0, sizeof(uint32_t), s);
@@ -376,13 +396,11 @@ int run_stream_decode(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, uin
         else (void)hipGetLastError();                                                // (out of memory for the scratch: the one-wave decoder needs none)
     }
     const size_t dec_cap = d_pass ? pass_cap : cap;
-    if (e == hipSuccess) e = codec_decode(algo, d_in, d_offsets, d_sizes, 1, d_out, dec_cap, dec_cap, false, nullptr, d_produced, d_err, ws + p.off_tables, zmap_bytes(algo, 1) ? reinterpret_cast<uint32_t*>(ws + p.off_zmap) : nullptr, s, d_pass);
+    if (e == hipSuccess) e = codec_decode(algo, d_in, d_offsets, d_sizes, 1, d_out, dec_cap, dec_cap, false, nullptr, d_produced, d_err, p.tables(ws), p.zmap(ws), s, d_pass);
     prof.mark(decode_kernel_name(algo));
     uint64_t h_prod = 0;
     uint32_t h_err = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_prod, d_produced, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = read_back(s, d_err, &h_err, &h_prod, d_produced, sizeof(h_prod));
     if (e != hipSuccess) { set_error("stream decode", e); return DENSITY_HIP_ERR_RUNTIME; }
     if (h_err) { set_error("truncated stream or output too small"); return DENSITY_HIP_ERR_FORMAT; }
     *size_out = (size_t)h_prod;
@@ -410,7 +428,7 @@ constexpr size_t kPipeMinStream = 32u << 20;
 size_t host_stream_encode_pipelined(DeviceCtx* c, const uint8_t* in, size_t n, uint8_t* out, size_t cap, bool* handled) {
     *handled = false;
     const size_t safe = safe_size(DENSITY_HIP_CHAMELEON, n);
-    if (n < kPipeMinStream || n >= (64ull << 30) || (g_variant & (5 | 512)) || g_rotor_unsafe || cap < safe) return 0;
+    if (n < kPipeMinStream || n >= (64ull << 30) || variant(kVarNoRotor | kVarPipeNever) || g_rotor_unsafe || cap < safe) return 0;
     const bool trace = debug_env("DENSITY_HIP_PROF") != nullptr;
     const double t0 = trace ? now_ms() : 0;
     PinnedInPlace pin_in(in, n), pin_out(out, safe);
@@ -426,9 +444,9 @@ size_t host_stream_encode_pipelined(DeviceCtx* c, const uint8_t* in, size_t n, u
     size_t per = (std::max<size_t>(n / want_slices, 2u << 20) + L.C - 1) / L.C;
     while ((S + per - 1) / per > kPipeMaxSlices) ++per;
     const uint32_t slices = (uint32_t)((S + per - 1) / per);
-    if (slices < 3 || !pipe_streams(c, 2 * slices) || pin_meta_ensure(c, S * 16 + 64) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    if (slices < 3 || !pipe_streams(c, 2 * slices) || c->pin_meta.ensure(S * 16 + 64) != hipSuccess) { (void)hipGetLastError(); return 0; }
     *handled = true;
-    uint64_t* p_sizes = reinterpret_cast<uint64_t*>(c->pin_meta);
+    uint64_t* p_sizes = reinterpret_cast<uint64_t*>(c->pin_meta.p);
     uint32_t* p_gfinal = reinterpret_cast<uint32_t*>(p_sizes + S);
     uint32_t* p_raw = p_gfinal + S;
     const uint8_t* d_in = (const uint8_t*)c->stage_in.p;
@@ -442,7 +460,7 @@ size_t host_stream_encode_pipelined(DeviceCtx* c, const uint8_t* in, size_t n, u
     uint64_t total = 0;
     size_t final_to = 0;                                                          // segments [0, final_to) are final, gathered and on their way down
     bool broke = false;
-    // a slice's verdicts: segments 0 and 1 started from the truth; k >= 2 is final iff every segment 1 .. k-1 coded all its blocks and k-1 ended calm.
+    // a slice's verdicts: segments 0 and 1 started from the truth; k >= 2 is final iff every segment 1 .. k-1 handed on the truth.
     // What is final goes down from where the device gathered it.
     auto verdicts = [&](uint32_t j) -> hipError_t {
         const size_t a = (size_t)j * per, b = std::min(S, a + per);
@@ -450,7 +468,7 @@ size_t host_stream_encode_pipelined(DeviceCtx* c, const uint8_t* in, size_t n, u
         if (x != hipSuccess) return x;
         if (trace) fprintf(stderr, "[density_hip prof]   slice %u verdicts at %.3f ms\n", j, now_ms() - t0);
         size_t k = a;
-        while (k < b && (k < 2 || (p_raw[k - 1] == 0 && (p_gfinal[k - 1] & 0x7fffffffu) == 0))) ++k;
+        while (k < b && (k < 2 || SegEncode::hands_on_truth(p_raw[k - 1], p_gfinal[k - 1]))) ++k;
         const uint64_t begin = total;
         for (size_t i = a; i < k; ++i) total += p_sizes[i];
         if (total > begin) x = hipMemcpyAsync(out + begin, d_out + begin, total - begin, hipMemcpyDeviceToHost, c->down);
@@ -461,14 +479,10 @@ size_t host_stream_encode_pipelined(DeviceCtx* c, const uint8_t* in, size_t n, u
     for (uint32_t j = 0; j < slices && e == hipSuccess && !broke; ++j) {
         const size_t a = (size_t)j * per, b = std::min(S, a + per);
         e = hipEventSynchronize(c->pipe_events[2 * j]);                           // the slice has arrived
-        // last writers of the slice's inner segments (every segment but the stream's first and last)
-        const size_t lw_a = std::max<size_t>(a, 1), lw_b = std::min(b, S - 1);
-        if (e == hipSuccess && lw_b > lw_a) e = launch_rotor_lastwriters(d_in + L.seg_at(lw_a), L.C, (uint32_t)(lw_b - lw_a), L.d_lw + lw_a * img, L.d_err, s);
+        if (e == hipSuccess) e = L.lastwriters(d_in, a, b, s);
         size_t sa = a;                                                            // the first speculating segment of the slice
         if (j == 0 && e == hipSuccess) {
-            SegArgs a0;                                                           // the stream's first segment: fresh tables, fresh FSM
-            a0.final_images = L.d_final; a0.final_guard = L.d_gfinal; a0.raw_blocks = L.d_raw;
-            e = launch_rotor_encode_seg(d_in, L.seg_len(0), L.C0, 1, L.d_stage, L.stride, L.d_sizes, L.d_err, a0, s);
+            e = launch_rotor_encode_seg(d_in, L.seg_len(0), L.C0, 1, L.d_stage, L.stride, L.d_sizes, L.d_err, L.reports(0), s);   // the stream's first segment: fresh tables, fresh FSM
             if (e == hipSuccess) e = hipMemcpyAsync(L.d_gspec + 1, L.d_gfinal, sizeof(uint32_t), hipMemcpyDeviceToDevice, s);   // the second starts from the true state
             sa = 1;
         }
@@ -485,16 +499,10 @@ size_t host_stream_encode_pipelined(DeviceCtx* c, const uint8_t* in, size_t n, u
     if (e == hipSuccess && !broke) e = verdicts(slices - 1);
     if (trace) fprintf(stderr, "[density_hip prof] pipelined stream encode: %zu segments of %zu bytes in %u slices, final up to segment %zu at %.3f ms\n", S, L.C, slices, final_to, now_ms() - t0);
     ++g_stream_stats[1];
-    // (always drained: nothing may still be reading or writing the caller's buffers when they are unpinned)
-    const hipError_t e1 = hipStreamSynchronize(c->up), e3 = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = e1 != hipSuccess ? e1 : e3;
+    e = drain(e, {c->up, s});                                                     // (whatever happened: see drain; the downloads go on beside what follows)
     if (e == hipSuccess && final_to < S) {
         // (every last-writer image the passes need is there: the slices behind the break were queued or are queued now)
-        for (uint32_t j = 0; j < slices && e == hipSuccess; ++j) {
-            const size_t a = (size_t)j * per, b = std::min(S, a + per);
-            const size_t lw_a = std::max<size_t>(std::max<size_t>(a, 1), final_to), lw_b = std::min(b, S - 1);
-            if (lw_b > lw_a) e = launch_rotor_lastwriters(d_in + L.seg_at(lw_a), L.C, (uint32_t)(lw_b - lw_a), L.d_lw + lw_a * img, L.d_err, s);
-        }
+        e = L.lastwriters(d_in, final_to, S, s);
         std::vector<uint64_t> h_sizes(S), h_offsets(S);
         size_t used = S;
         if (e == hipSuccess) e = seg_encode_passes(L, d_in, final_to, s, h_sizes, &used, trace);
@@ -507,10 +515,9 @@ size_t host_stream_encode_pipelined(DeviceCtx* c, const uint8_t* in, size_t n, u
             if (e == hipSuccess && total > begin) e = hipMemcpyAsync(out + begin, d_out + begin, total - begin, hipMemcpyDeviceToHost, c->down);
         }
     }
-    const hipError_t e5 = hipStreamSynchronize(c->down);
-    if (e == hipSuccess) e = e5;
+    e = drain(e, {c->down});
     uint32_t h_err = 0;
-    if (e == hipSuccess) e = hipMemcpy(&h_err, L.d_err, sizeof(h_err), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = read_back(s, L.d_err, &h_err);
     if (e != hipSuccess) { set_error("stream encode (pipelined host path)", e); return 0; }
     if (h_err) { set_error("stream encode: device-side watchdog"); return 0; }
     if (trace) fprintf(stderr, "[density_hip prof]   all down at %.3f ms\n", now_ms() - t0);
@@ -528,7 +535,7 @@ size_t host_stream_encode_pipelined(DeviceCtx* c, const uint8_t* in, size_t n, u
 size_t host_stream_decode_pipelined(DeviceCtx* c, const uint8_t* in, size_t E, uint8_t* out, size_t cap, bool* handled, bool* uploaded) {
     *handled = false;
     *uploaded = false;
-    if (E < kPipeMinStream / 2 || E >= (1ull << 32) || (g_variant & (5 | 512)) || g_rotor_unsafe || cap == 0) return 0;
+    if (E < kPipeMinStream / 2 || E >= (1ull << 32) || variant(kVarNoRotor | kVarPipeNever) || g_rotor_unsafe || cap == 0) return 0;
     cap = std::min<size_t>(cap, (E / 136 + 2) * 256);                              // what the stream can decode to: 256 bytes per record of 136 bytes and more
     const size_t bound = cap;
     SegDecode D;
@@ -543,7 +550,7 @@ size_t host_stream_decode_pipelined(DeviceCtx* c, const uint8_t* in, size_t E, u
     if (slices < 3 || slices > kPipeMaxSlices) return 0;
     PinnedInPlace pin_in(in, E), pin_out(out, bound);
     if (!pin_in || !pin_out) return 0;
-    if (!pipe_streams(c, 2 * slices + 2) || pin_meta_ensure(c, 4096) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    if (!pipe_streams(c, 2 * slices + 2) || c->pin_meta.ensure(4096) != hipSuccess) { (void)hipGetLastError(); return 0; }
     e = c->stage_in.ensure(E);
     if (e == hipSuccess) e = c->stage_out.ensure(bound);
     if (e != hipSuccess) { (void)hipGetLastError(); return 0; }
@@ -551,11 +558,11 @@ size_t host_stream_decode_pipelined(DeviceCtx* c, const uint8_t* in, size_t E, u
     const double t0 = trace ? now_ms() : 0;
     uint8_t* d_in = (uint8_t*)c->stage_in.p;
     uint8_t* d_out = (uint8_t*)c->stage_out.p;
-    uint32_t* p_info = reinterpret_cast<uint32_t*>(c->pin_meta);                  // 16 words back, then three words per slice up
-    uint64_t* p_last = reinterpret_cast<uint64_t*>(c->pin_meta + 64);
-    uint32_t* p_err = reinterpret_cast<uint32_t*>(c->pin_meta + 80);
-    uint64_t* p_open = reinterpret_cast<uint64_t*>(c->pin_meta + 96);
-    uint32_t* p_start = reinterpret_cast<uint32_t*>(c->pin_meta + 128);
+    uint32_t* p_info = reinterpret_cast<uint32_t*>(c->pin_meta.p);                  // 16 words back, then three words per slice up
+    uint64_t* p_last = reinterpret_cast<uint64_t*>(c->pin_meta.p + 64);
+    uint32_t* p_err = reinterpret_cast<uint32_t*>(c->pin_meta.p + 80);
+    uint64_t* p_open = reinterpret_cast<uint64_t*>(c->pin_meta.p + 96);
+    uint32_t* p_start = reinterpret_cast<uint32_t*>(c->pin_meta.p + 128);
     hipStream_t s = c->stream, q = c->kern[1];                                     // the parse, slice by slice | the segments' kernels behind it
     e = hipMemsetAsync(D.d_chunk_offset, 0, (D.max_chunks + 2) * sizeof(uint64_t), s);
     if (e == hipSuccess) e = hipMemsetAsync(D.d_info, 0, 18 * sizeof(uint32_t), s);
@@ -572,6 +579,13 @@ size_t host_stream_decode_pipelined(DeviceCtx* c, const uint8_t* in, size_t E, u
     size_t done = 0, n_chunks = 0;                                                // segments decoded so far; of the whole stream (known behind the last slice)
     size_t down_from = 0, down_bytes = 0;                                         // output that is being made and has yet to go down
     uint32_t down_slice = 0;
+    const auto send_down = [&] {                                                  // a slice's segments' output goes down once they are through
+        if (!down_bytes) return hipSuccess;
+        hipError_t x = hipEventSynchronize(c->pipe_events[2 * down_slice + 1]);
+        if (x == hipSuccess) x = hipMemcpyAsync(out + down_from, d_out + down_from, down_bytes, hipMemcpyDeviceToHost, c->down);
+        down_bytes = 0;
+        return x;
+    };
     for (uint32_t j = 0; j < slices && e == hipSuccess && !give_up; ++j) {
         const bool last = j + 1 == slices;
         const size_t have = last ? E : (size_t)(j + 1) * slice;
@@ -580,11 +594,7 @@ size_t host_stream_decode_pipelined(DeviceCtx* c, const uint8_t* in, size_t E, u
         if (e == hipSuccess) e = hipMemcpyAsync(D.d_info + 8, p_start + 3 * j, 12, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = launch_stream_parse(d_in, have, from_pos, D.base, D.d_index, D.max_chunks * kCB, D.d_chunk_offset, (uint32_t)kCB, D.d_pos32, D.d_info, s);
         if (e == hipSuccess) e = hipMemcpyAsync(p_info, D.d_info, 64, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && down_bytes) {                                      // the slice in front: its segments' output goes down once they are through
-            e = hipEventSynchronize(c->pipe_events[2 * down_slice + 1]);
-            if (e == hipSuccess) e = hipMemcpyAsync(out + down_from, d_out + down_from, down_bytes, hipMemcpyDeviceToHost, c->down);
-            down_bytes = 0;
-        }
+        if (e == hipSuccess) e = send_down();                                     // the slice in front
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) break;
         // (from here on this slice's segments are `q`'s business, beside the next slice's parse on `s` — which rewrites the entries of block whole - 1
@@ -611,18 +621,8 @@ size_t host_stream_decode_pipelined(DeviceCtx* c, const uint8_t* in, size_t E, u
             }
             const uint64_t range_end = last ? (uint64_t)E : (whole % kCB == 0 ? end_pos : ~0ull);
             if (e == hipSuccess) e = launch_seg_layout(D.d_chunk_offset, (uint32_t)done, (uint32_t)count, range_end, D.d_offsets, D.d_sizes, D.d_err, q);
-            SegArgs lw;
-            lw.final_images = D.d_lw + done * img;
-            lw.lastwriters_only = 1;
-            if (e == hipSuccess) e = launch_rotor_decode_seg(d_in, D.d_offsets + done, D.d_sizes + done, (uint32_t)count, d_out + out_off, kCBy, out_total, D.d_index + done * kCB,
-                                                             D.d_zmap + done * kZmapWordsPerChunk, D.d_produced + done, D.d_err + 1, lw, q);
-            // start images of the range and, one more, the image the next range starts from
-            if (e == hipSuccess) e = launch_merge_images(D.d_carry, D.d_lw + done * img, D.d_start + done * img, (uint32_t)count + 1, q);
-            if (e == hipSuccess) e = hipMemcpyAsync(D.d_carry, D.d_start + upto * img, img, hipMemcpyDeviceToDevice, q);
-            SegArgs real;
-            real.init_images = D.d_start + done * img;
-            if (e == hipSuccess) e = launch_rotor_decode_seg(d_in, D.d_offsets + done, D.d_sizes + done, (uint32_t)count, d_out + out_off, kCBy, out_total, D.d_index + done * kCB,
-                                                             D.d_zmap + done * kZmapWordsPerChunk, D.d_produced + done, D.d_err, real, q);
+            // (start images of the range and, one more, the image the next range starts from)
+            if (e == hipSuccess) e = D.decode_range(d_in, done, count, d_out + out_off, out_total, D.d_carry, true, q);
             if (e == hipSuccess) e = hipEventRecord(c->pipe_events[2 * j + 1], q);
             const size_t full = last ? count - 1 : count;                         // (the stream's last segment goes down once its length is known)
             down_from = out_off; down_bytes = full * kCBy; down_slice = j;
@@ -635,11 +635,7 @@ size_t host_stream_decode_pipelined(DeviceCtx* c, const uint8_t* in, size_t E, u
         if (done != n_chunks || n_chunks == 0) give_up = true;
         else {
             e = hipMemcpyAsync(p_last, D.d_produced + (n_chunks - 1), 8, hipMemcpyDeviceToHost, q);
-            if (e == hipSuccess && down_bytes) {
-                e = hipEventSynchronize(c->pipe_events[2 * down_slice + 1]);
-                if (e == hipSuccess) e = hipMemcpyAsync(out + down_from, d_out + down_from, down_bytes, hipMemcpyDeviceToHost, c->down);
-                down_bytes = 0;
-            }
+            if (e == hipSuccess) e = send_down();
             if (e == hipSuccess) e = hipMemcpyAsync(p_err, D.d_err, 4, hipMemcpyDeviceToHost, q);
             if (e == hipSuccess) e = hipStreamSynchronize(q);
             if (e == hipSuccess && (*p_err || *p_last > kCBy || (n_chunks - 1) * kCBy + *p_last > cap)) give_up = true;   // (the staged call words the refusal)
@@ -649,9 +645,7 @@ size_t host_stream_decode_pipelined(DeviceCtx* c, const uint8_t* in, size_t E, u
             }
         }
     }
-    // (always drained: nothing may still be reading or writing the caller's buffers when they are unpinned)
-    const hipError_t e1 = hipStreamSynchronize(c->up), e2 = hipStreamSynchronize(s), e2b = hipStreamSynchronize(q), e3 = hipStreamSynchronize(c->down);
-    if (e == hipSuccess) e = e1 != hipSuccess ? e1 : e2 != hipSuccess ? e2 : e2b != hipSuccess ? e2b : e3;
+    e = drain(e, {c->up, s, q, c->down});
     if (e != hipSuccess) { (void)hipGetLastError(); return 0; }                   // (handled stays false: the staged call reports what is wrong)
     if (give_up) { *uploaded = true; if (trace) fprintf(stderr, "[density_hip prof]   -> staged path (the stream stays where it is: on the device)\n"); return 0; }
     if (trace) fprintf(stderr, "[density_hip prof]   %zu segments of %zu bytes, all down at %.3f ms\n", n_chunks, kCBy, now_ms() - t0);
@@ -679,9 +673,7 @@ size_t host_stream_codec(int algo, bool encode, const uint8_t* in, size_t n, uin
         if (handled) return r;
     }
     const size_t dev_cap = encode ? safe_size(algo, n) : cap;
-    hipError_t e = c->stage_in.ensure(n);
-    if (e == hipSuccess) e = c->stage_out.ensure(dev_cap ? dev_cap : 1);
-    if (e == hipSuccess) e = c->work.ensure(plan_decode(algo, 1).total + kAlign);
+    hipError_t e = ensure_staging(c, n, dev_cap ? dev_cap : 1, plan_decode(algo, 1).total + kAlign);
     if (e == hipSuccess && !uploaded) e = copy_host_side_pinned(c->stage_in.p, in, n, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) { set_error("staging (H2D)", e); return 0; }
     size_t produced = 0;
@@ -694,6 +686,20 @@ size_t host_stream_codec(int algo, bool encode, const uint8_t* in, size_t n, uin
         if (e != hipSuccess) { set_error("staging (D2H)", e); return 0; }
     }
     return produced;
+}
+
+// the two density_hip_stream_*_device symbols
+int stream_device(bool encode, int algo, const void* d_input, size_t input_size, void* d_output, size_t output_capacity, void* stream, size_t* size_out) {
+    g_last_error.clear();
+    if (!valid_algo(algo) || !size_out || (!d_input && input_size) || (!d_output && output_capacity)) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return DENSITY_HIP_ERR_RUNTIME;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const size_t need = plan_decode(algo, 1).total + kAlign;
+    uint8_t* ws = nullptr;
+    if (const int rc = resolve_workspace(c, nullptr, 0, need, need, &ws)) return rc;
+    return (encode ? run_stream_encode : run_stream_decode)(c, algo, (const uint8_t*)d_input, input_size, (uint8_t*)d_output, output_capacity, ws,
+                                                            stream ? (hipStream_t)stream : c->stream, size_out);
 }
 
 }  // namespace api
@@ -717,28 +723,11 @@ size_t lion_safe_encode_buffer_size(size_t size) { return safe_size(DENSITY_HIP_
 
 int density_hip_stream_encode_device(int algo, const void* d_input, size_t input_size, void* d_output, size_t output_capacity,
                                      void* stream, size_t* size_out) {
-    g_last_error.clear();
-    if (!valid_algo(algo) || !size_out || (!d_input && input_size) || (!d_output && output_capacity)) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
-    DeviceCtx* c = acquire_ctx();
-    if (!c) return DENSITY_HIP_ERR_RUNTIME;
-    std::lock_guard<std::mutex> lk(c->mu);
-    hipError_t e = c->work.ensure(plan_decode(algo, 1).total + kAlign);
-    if (e != hipSuccess) { set_error("workspace allocation", e); return DENSITY_HIP_ERR_RUNTIME; }
-    return run_stream_encode(c, algo, (const uint8_t*)d_input, input_size, (uint8_t*)d_output, output_capacity, (uint8_t*)c->work.p,
-                             stream ? (hipStream_t)stream : c->stream, size_out);
+    return stream_device(true, algo, d_input, input_size, d_output, output_capacity, stream, size_out);
 }
-
 int density_hip_stream_decode_device(int algo, const void* d_input, size_t input_size, void* d_output, size_t output_capacity,
                                      void* stream, size_t* size_out) {
-    g_last_error.clear();
-    if (!valid_algo(algo) || !size_out || (!d_input && input_size) || (!d_output && output_capacity)) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
-    DeviceCtx* c = acquire_ctx();
-    if (!c) return DENSITY_HIP_ERR_RUNTIME;
-    std::lock_guard<std::mutex> lk(c->mu);
-    hipError_t e = c->work.ensure(plan_decode(algo, 1).total + kAlign);
-    if (e != hipSuccess) { set_error("workspace allocation", e); return DENSITY_HIP_ERR_RUNTIME; }
-    return run_stream_decode(c, algo, (const uint8_t*)d_input, input_size, (uint8_t*)d_output, output_capacity, (uint8_t*)c->work.p,
-                             stream ? (hipStream_t)stream : c->stream, size_out);
+    return stream_device(false, algo, d_input, input_size, d_output, output_capacity, stream, size_out);
 }
 
 }  // extern "C"

@@ -238,7 +238,7 @@ def _host_containers(algo, n, chunk, kv, variant):
 
 @pytest.mark.parametrize("algo", ["chameleon", "cheetah", "lion"])
 def test_reference_symbols_on_host_slices(algo, variant):
-    """{algo}_encode with output_size = the oracle's exact length (succeeds: api_stream.hip:691 checks what was produced), that length - 1 (0, the
+    """{algo}_encode with output_size = the oracle's exact length (succeeds: host_stream_codec in api_stream.hip checks what was produced), that length - 1 (0, the
     buffer untouched) and the safe size; {algo}_decode with n - 1 (0), n and n + 100 (n, the 100 bytes behind untouched) — input and output
     numpy slices at offsets 1, 3, 4 and 12 of guarded arrays."""
     for kv in (0, 512):
@@ -320,7 +320,7 @@ def test_misaligned_device_containers(algo, n, chunk, kind, variant):
                 assert taken == (n_chunks if io % 4 == 0 else 0), (where, "exchange passes", taken)      # exchange_stages.hip: d_in % 4
             if form == "paged":
                 paged = bool(hdr.flags & container.FLAG_PAGED)
-                assert paged == _paged_layout_ok(algo, n, chunk, io), (where, hdr.flags)            # api.hip:161: a misaligned input comes out slotted
+                assert paged == _paged_layout_ok(algo, n, chunk, io), (where, hdr.flags)            # settle_form in api.hip: a misaligned input comes out slotted
                 if not paged:
                     assert hdr.flags & container.FLAG_SLOTTED and np.array_equal(blob, ref["slotted"]), where
                 _, payloads = container.chunk_payloads(blob)
@@ -335,7 +335,7 @@ def test_misaligned_device_containers(algo, n, chunk, kind, variant):
             where = f"decode of the {form} container at +{oo} to +{io}"
             if form == "paged" and hdr.flags & container.FLAG_PAGED:
                 pages_base = _pages_base(blob)
-                if io % 4 or (oo + pages_base) % 4 or (oo + _index_at(hdr)) % 4:             # api.hip:277: the paged decoder reads pages in place, 4-byte aligned
+                if io % 4 or (oo + pages_base) % 4 or (oo + _index_at(hdr)) % 4:             # run_decode_container in api.hip: the paged decoder reads pages in place, 4-byte aligned
                     assert rc == _lib.ERR_UNSUPPORTED, (where, rc)
                     back.untouched(where)
                     continue
@@ -393,7 +393,7 @@ def test_misaligned_chameleon_pipelines(io, oo, variant):
 @pytest.mark.parametrize("algo", ["chameleon", "cheetah", "lion"])
 def test_misaligned_device_streams(algo, kind):
     """stream_encode_device / stream_decode_device at the offsets of PAIRS: the oracle's stream, the input back, poison and guards intact.
-    Chameleon's segmented encode takes 4-byte aligned inputs only (api_stream.hip:168), its segmented decode 4-byte aligned outputs; Cheetah's
+    Chameleon's segmented encode takes 4-byte aligned inputs only (run_stream_encode in api_stream.hip), its segmented decode 4-byte aligned outputs; Cheetah's
     decode passes 4-byte aligned outputs."""
     n = STREAM_SIZES[algo]
     data = _data(kind, n, seed=5)
@@ -506,7 +506,7 @@ def test_exact_stream_capacities(algo):
 def test_exact_dirty_workspaces(algo, n, chunk):
     """A workspace of exactly density_hip_encode_workspace_size / density_hip_decode_workspace_size_for bytes, poisoned before the first call and
     guarded behind, serves two calls back to back (the second on the first one's leftovers); one byte less is ERR_CAPACITY (a Cheetah decode
-    instead leaves the decode passes to the one-wave decoder: api.hip:264)."""
+    instead leaves the decode passes to the one-wave decoder: DecodePlan::pass in api_internal.hpp)."""
     data = _data("mixed", n, seed=21)
     want = _chunk_streams(algo, data, chunk)
     src = Region(n, 0, fill=data)
@@ -552,7 +552,7 @@ def test_exact_dirty_workspaces(algo, n, chunk):
         assert decode_rc(out.ptr, hdr.container_len, back.ptr, n, ws=(mini.ptr, bare)) == (_lib.OK, n)
         mini.check("decode_workspace_size workspace")
         assert np.array_equal(back.check("decode on decode_workspace_size"), data)
-        # the passes whenever the workspace also holds their scratch (api.hip:264): decode_workspace_size() is sized for Lion's tables,
+        # the passes whenever the workspace also holds their scratch (DecodePlan::pass in api_internal.hpp): decode_workspace_size() is sized for Lion's tables,
         # which for a few chunks exceeds what Cheetah's passes need
         assert L().density_hip_decode_pass_count() - c0 == (1 if bare >= dws else 0), (bare, dws)
         # chunks of 1 MiB: there decode_workspace_size() cannot hold the passes' scratch, and the one-wave decoder serves the call
