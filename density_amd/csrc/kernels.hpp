@@ -36,14 +36,14 @@ hipError_t launch_chameleon_decode(const uint8_t* d_in, const uint64_t* d_offset
 // kMaxPipelinedChunks chunks (more chunks than that, i.e. tiny chunks, run on the one-wavefront kernel)
 constexpr uint32_t kZmapWordsPerChunk = 2048, kMaxPipelinedChunks = 16384;
 
-// ---- rotor.hip (Chameleon wave-rotation kernels: the default encode / index-fed decode path) ----
+// ---- rotor.hip, rotor_encode.hip, rotor_decode.hip (Chameleon wave-rotation kernels: the default encode / index-fed decode path) ----
 // pages of a paged container: 64 KiB — a round of 16 blocks is at most 4224 bytes, so a page's unused tail is below 7 % and 2 % on average
 constexpr uint32_t kPageShift = 16, kPageBytes = 1u << kPageShift;
 // pages one chunk can need (a page is left when the next round's records do not fit: at most a round's worth unused per page), and the words of
 // its directory
 __host__ __device__ inline uint32_t pages_per_chunk(uint64_t worst_stream_bytes) { return (uint32_t)(worst_stream_bytes / (kPageBytes - 4352u)) + 2u; }
 __host__ __device__ inline uint32_t page_dir_words(uint32_t pages) { return 4u * (pages + 1u); }
-// what the paged DECODER takes (rotor.hip: kRotMaxBlocks blocks of index, kDecMaxPages directory entries in LDS): the encoder offers no more
+// what the paged DECODER takes (rotor_dev.hpp: kRotMaxBlocks blocks of index, kDecMaxPages directory entries in LDS): the encoder offers no more
 constexpr uint64_t kPagedMaxChunk = 4ull << 20;
 constexpr uint32_t kPagedMaxPages = 96;
 bool rotor_encode_eligible(const uint8_t* d_in, uint64_t total, uint64_t chunk_bytes, uint32_t n_chunks);
@@ -57,7 +57,7 @@ hipError_t launch_rotor_encode(const uint8_t* d_in, uint64_t total, uint64_t chu
 constexpr uint64_t kSegImageBytes = 128ull * 1024 + 8ull * 1024;
 struct SegArgs {
     const uint8_t* init_images = nullptr;   // per chunk kSegImageBytes, or nullptr: fresh tables
-    const uint32_t* init_guard = nullptr;   // per chunk: packed FSM state (rotor.hip::pack_guard); bit 31: start in speculation (fast) mode
+    const uint32_t* init_guard = nullptr;   // per chunk: packed FSM state (rotor_dev.hpp::pack_guard); bit 31: start in speculation (fast) mode
     uint8_t* final_images = nullptr;        // per chunk: the dictionary image after the chunk
     uint32_t* final_guard = nullptr;        // per chunk: the FSM state after the chunk's last whole block
     uint32_t* raw_blocks = nullptr;         // per chunk: number of raw-copy blocks (pre-zeroed by the caller)
@@ -90,7 +90,7 @@ hipError_t launch_rotor_decode(const uint8_t* d_in, const uint64_t* d_offsets, c
                                uint64_t* d_produced, uint32_t* d_err, hipStream_t stream);
 // LDS assumptions of the rotation kernels (ordered exchange lane order, token hand-off behind the exchanges, lane-reversed rollback)
 hipError_t launch_rotor_selftest(uint32_t* d_fail, hipStream_t stream);
-constexpr bool kRotorSplitDefault = false;   // which rotation encoder ships: the split one (8 chain + 8 emit waves, rotor.hip) or the 8-wave one
+constexpr bool kRotorSplitDefault = false;   // which rotation encoder ships: the split one (8 chain + 8 emit waves, rotor_encode.hip) or the 8-wave one
 extern bool g_rotor_split;     // density_hip_set_kernel_variant(2048): the OTHER rotation encoder than kRotorSplitDefault (A/B runs, cross-checks)
 extern bool g_force_pipeline;  // density_hip_set_kernel_variant(4): the 16-wave role pipelines of chameleon.hip instead
 extern bool g_exchange_unsafe, g_rotor_unsafe;   // start-up self-test verdicts (api.hip::acquire_ctx)

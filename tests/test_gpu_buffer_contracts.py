@@ -6,7 +6,7 @@ poison (never zeros), the library gets `base + offset`, and after the call both 
 the capacity lands in a guard (the back guard is at least what a wrong kernel could write past the capacity plus 64 KiB), not outside the
 allocation.  Decode outputs keep their poison in [decoded length, capacity): the reference writes only what it decodes.
 
-The library picks kernels by alignment (rotor.hip: rotor_encode_eligible / rotor_decode_eligible, chameleon.hip: the 16-wave pipelines,
+The library picks kernels by alignment (rotor_encode.hip / rotor_decode.hip: rotor_encode_eligible / rotor_decode_eligible, chameleon.hip: the 16-wave pipelines,
 exchange_stages.hip: stage_encode_eligible, decode_passes.hip: decode_pass_eligible, api.hip: the paged decoder, api_stream.hip: the segmented
 stream encode), so the offsets below put each call on both sides of each gate; 4, 8 and 12 pass every `% 4` gate at addresses that are not
 16-byte aligned.  Where a counter says which path served a call (density_hip_decode_pass_count, density_hip_stage_stats under variant 64,

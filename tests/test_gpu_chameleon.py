@@ -23,7 +23,7 @@ VARIANTS = {"rotor": 0, "rotor-noindex": 2, "pipelined": 4, "pipelined-noindex":
 
 @pytest.fixture(autouse=True, params=list(VARIANTS))
 def kernel_variant(request):
-    """Every test runs against the default wave-rotation kernels (rotor.hip; containers with the block index = index-fed rotation
+    """Every test runs against the default wave-rotation kernels (rotor_encode.hip / rotor_decode.hip; containers with the block index = index-fed rotation
     decoder, without it = record-walking decoder), the 16-wave role pipelines (chameleon.hip, with and without the index) and the
     one-wavefront kernels: three independent implementations of the same stream semantics cross-checking each other."""
     container.set_kernel_variant(VARIANTS[request.param])
@@ -228,7 +228,7 @@ def test_corrupt_block_index_is_a_format_error(kernel_variant):
         bad[base + b] = (int(bad[base + b]) + int(rng.integers(1, 5))) % 65
         with pytest.raises(DecodeError):
             container.decode(bad, out)
-    # the raw-copy bits are checked against the blow-up protection (rotor.hip::index_fsm_consistent): a coded block flagged raw, a raw block
+    # the raw-copy bits are checked against the blow-up protection (rotor_decode.hip::index_fsm_consistent): a coded block flagged raw, a raw block
     # flagged coded, on calm text and on data with raw copies in it — wrong bytes of the right length would otherwise come back as OK
     for kind, seed in (("prose", 9), ("mixed", 19), ("random", 29)):
         data = datagen.by_kind(kind, n, seed=seed)
@@ -420,7 +420,7 @@ def test_abort_and_recovery_paths(kernel_variant):
 
 
 def test_long_incompressible_stretches_and_their_ends(kernel_variant):
-    """Stretches of incompressible data LONG enough for the encoder's ordered rounds to run ahead of their commit (rotor.hip: three rounds of one
+    """Stretches of incompressible data LONG enough for the encoder's ordered rounds to run ahead of their commit (rotor_encode.hip: three rounds of one
     unbroken stretch, 12 KiB, start it), ended by data that compresses — where the round that ran ahead finds its assumption wrong, raises the abort and
     the waves behind it take back exactly the blocks that exchanged — by zeros, by low-entropy noise, by the chunk's end; at chunk sizes from one round of
     run-ahead to the headline's 4 MiB, as container (every chunk stream == the oracle's) and as one stream."""

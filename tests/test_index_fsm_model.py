@@ -1,4 +1,4 @@
-"""The local rules by which the rotation decoder validates the raw-copy bits of a block index (rotor.hip::index_fsm_consistent,
+"""The local rules by which the rotation decoder validates the raw-copy bits of a block index (rotor_decode.hip::index_fsm_consistent,
 restated in tools/index_fsm_model.py) accept exactly the indexes a walk of the reference's blow-up protection FSM accepts."""
 import os
 import sys

@@ -1,6 +1,6 @@
-"""Build-time check of the hand-fetched quads in the rotation encoder (rotor.hip: prefetch_quads / quads_landed).
+"""Build-time check of the hand-fetched quads in the rotation encoder (rotor_encode.hip: prefetch_quads / quads_landed).
 
-The next round's quads are loaded by hand into the wave's R highest registers (v(256-R)..v255, 8-wave kernels) and read out of
+The next round's quads are loaded by hand into the wave's 16 highest registers (v240..v255: rounds of 16 blocks, 8 waves) and read out of
 them, behind a hand-counted wait, by one later statement; the compiler knows the registers only as clobbered by both
 statements.  The scheme is sound as long as the compiler itself never puts a value there, which it has no reason to (it
 allocates upwards from v0 and these kernels need fewer than 240 registers) but is not forced to.  This script disassembles
@@ -71,6 +71,7 @@ def row_pairs(body):
     return found
 
 LLVM = "/opt/rocm/lib/llvm/bin"
+ENC_ROUND, DEC_ROUND = 16, 12   # rotor_dev.hpp: kEncRound, kDecRound (blocks / records per round; the kernels' names no longer carry them)
 
 def shipped_code(lib):
     """Disassembly and kernel metadata of the code objects INSIDE the built library (what ships is what is checked: not a second
@@ -109,13 +110,13 @@ def main():
     funcs, notes = shipped_code(lib)
     total = bad = 0
     for name, body in funcs.items():
-        # every encoder instance with kept quads (last template argument): 8 waves stage in v(256-R)..v255, 12 waves in v(168-R)..v167
-        ms = re.match(r"^_ZN7density20chameleon_encode_rotILi(\d+)ELi(\d+)ELb[01]ELb0ELb0ELb[01]ELb1EE", name)   # (<R, W, kProf, KEEP, EARLY, PAGED, SPLIT>: the split encoder)
+        # every encoder instance with kept quads (last template argument false): 8 waves, staging in v240..v255
+        ms = re.match(r"^_ZN7density20chameleon_encode_rotILb[01]ELb[01]ELb1EE", name)   # (<kProf, PAGED, SPLIT>: the split encoder)
         if ms:
             # sixteen waves share the CU: 128 registers each.  The common path of a chain wave must not touch scratch memory (a reload between the
             # token and the first exchange is hundreds of cycles of the critical section): from the ring's reads to the round's exchanges nothing but
             # what the rare paths (laid out in between) need — a handful of spills in all, none of them next to the exchanges
-            R = int(ms.group(1))
+            R = ENC_ROUND
             first = next((k for k, t in enumerate(body) if t.startswith("ds_mskor_rtn_b32")), None)
             near = [t for t in body[max(0, (first or 0) - 12):(first or 0) + R + 4] if t.startswith("scratch_")]
             spills = sum(t.startswith("scratch_") for t in body)
@@ -143,21 +144,21 @@ def main():
                 bad += 1
             total += hand
             continue
-        m = re.match(r"^_ZN7density20chameleon_encode_rotILi(\d+)ELi(\d+)ELb[01]ELb1ELb[01]ELb[01]ELb0EE", name)   # (<R, W, kProf, KEEP, EARLY, PAGED, SPLIT>)
+        m = re.match(r"^_ZN7density20chameleon_encode_rotILb[01]ELb[01]ELb0EE", name)   # (<kProf, PAGED, SPLIT>)
         if not m:
             continue
-        g, b = check_function(name, int(m.group(1)), body, 256 if int(m.group(2)) == 8 else 168)
+        g, b = check_function(name, ENC_ROUND, body)
         total += g; bad += b
     # the decoder's exact waits: stage B must wait for "all but the last 12 (stores)", not for everything (a branch around the record stores,
     # a load left pending across the loop head ... turn it into vmcnt(0) and cost 5-10 % without a test failing)
     dec = 0
     for name, body in funcs.items():
-        m = re.match(r"^_ZN7density20chameleon_decode_rotILi(\d+)ELi(\d+)ELb0E", name)       # every shipped geometry (rounds of R records: R stores per round)
-        if not m or int(m.group(1)) < 12:
+        m = re.match(r"^_ZN7density20chameleon_decode_rotILb0ELb[01]EE", name)       # (<kProf, PAGED>; rounds of 12 records: 12 stores per round)
+        if not m:
             continue
-        want = f"s_waitcnt vmcnt({m.group(1)})"
+        want = f"s_waitcnt vmcnt({DEC_ROUND})"
         first = next(k for k, t in enumerate(body) if t.startswith("ds_mskor_rtn_b32"))
-        window = body[max(0, first - 75 * int(m.group(1))):first]
+        window = body[max(0, first - 75 * DEC_ROUND):first]
         waits = [t for t in window if t.startswith("s_waitcnt vmcnt(") and "lgkmcnt" not in t]
         if want not in waits:
             print(f"{name}: stage B no longer waits with {want}: {waits}")

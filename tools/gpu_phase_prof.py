@@ -1,4 +1,4 @@
-"""Phase profile (debug build, DENSITY_HIP_PROF=1: work-group 0's cycle accounting and event counts, rotor.hip PhaseClock) of the rotation kernels on one
+"""Phase profile (debug build, DENSITY_HIP_PROF=1: work-group 0's cycle accounting and event counts, rotor_dev.hpp PhaseClock) of the rotation kernels on one
 data kind:    python tools/gpu_phase_prof.py [text|zeros|random|mixed] [MiB] [chunk KiB] [kernel variant]"""
 import os, sys
 os.environ.setdefault("DENSITY_HIP_PROF", "1")

@@ -1,4 +1,4 @@
-"""Phase profile (debug build, DENSITY_HIP_PROF=1: work-group 0's cycle accounting, rotor.hip PhaseClock) of the two rotation encoders on the headline workload:
+"""Phase profile (debug build, DENSITY_HIP_PROF=1: work-group 0's cycle accounting, rotor_dev.hpp PhaseClock) of the two rotation encoders on the headline workload:
     DENSITY_HIP_PROF=1 python tools/gpu_split_prof.py"""
 import os, sys
 os.environ.setdefault("DENSITY_HIP_PROF", "1")

@@ -1,7 +1,7 @@
 """Same-box, same-buffers A/B of experiment builds (tools/build_variant.sh -> probes/variants/lib_*.so) against the tree's library: kernel times of
 the headline workload's ENCODE and DECODE separately, HIP events, no correctness claim for the variants (the decode leg of every library
 reads the container the tree's library made and is checked; experiment encoders may write garbage — their output goes to a scratch buffer).
-    python tools/gpu_variants.py [steps] [name ...]        (names: probes/variants/lib_<name>.so; DENSITY_HIP_TUNE applies to all of them)"""
+    python tools/gpu_variants.py [steps] [name ...]        (names: probes/variants/lib_<name>.so; DENSITY_HIP_TUNE — bit 0, the self-test's token behind the answers — applies to all of them)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

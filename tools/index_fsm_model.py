@@ -1,4 +1,4 @@
-"""The rotation decoder's check of a block index's raw-copy bits (rotor.hip::index_fsm_consistent), restated in Python, next to the
+"""The rotation decoder's check of a block index's raw-copy bits (rotor_decode.hip::index_fsm_consistent), restated in Python, next to the
 plain walk of the blow-up protection FSM it must be equivalent to (protection_state.rs:19-47, codec.rs:89-91).
 
 An index entry: bit 7 = raw-copy block, bits 0..6 = MAP count of a coded block (0x7f: the ragged last block).  A coded block is
@@ -37,7 +37,7 @@ def _halve(s, k):
 
 
 def block_consistent(ix, i):
-    """rotor.hip::index_fsm_consistent for block i (called where the block is raw or incompressible)."""
+    """rotor_decode.hip::index_fsm_consistent for block i (called where the block is raw or incompressible)."""
     n = len(ix)
     raw = lambda b: bool(ix[b] & 0x80)
     inc = lambda b: ix[b] <= 4

@@ -1,4 +1,4 @@
-"""Offline look at a DENSITY_HIP_PROF_DUMP (rotor.hip: rot_prof_report): hop / iteration / lateness statistics per wave.
+"""Offline look at a DENSITY_HIP_PROF_DUMP (rotor.hip::rot_prof_report): hop / iteration / lateness statistics per wave.
 usage: python tools/prof_stamps.py <prefix> [decode_waves decode_rounds_of]"""
 import sys
 import numpy as np
