@@ -18,6 +18,25 @@ extern "C" {
     fn lion_safe_encode_buffer_size(size: usize) -> usize;
 }
 
+/// include/density_hip.h section 2, sealed containers (DENSITY_HIP_FLAG_CHECKSUM): what a CPU reader and a host-pointer producer link.  The device-pointer calls
+/// (density_hip_checksum_device, density_hip_seal_device) take a hipStream_t and belong to a caller that already binds HIP; they are declared here in step with the header.
+pub mod sealed {
+    pub const DENSITY_HIP_FLAG_CHECKSUM: u16 = 8;
+    pub const DENSITY_HIP_ERR_CHECKSUM: i32 = 6;
+    #[repr(C)]
+    pub struct DensityHipHeader { pub magic: u32, pub algo: u8, pub version: u8, pub flags: u16, pub chunk_size: u32, pub n_chunks: u32, pub total_len: u64, pub container_len: u64 }
+    #[link(name = "density_hip")]
+    extern "C" {
+        /// C of one decoded chunk, host arithmetic (no device): compare with trailer entry i at container_len - round_up(4 * n_chunks, 16) + 4 * i
+        pub fn density_hip_checksum32(data: *const u8, size: usize) -> u32;
+        pub fn density_hip_seal_overhead(input_size: usize, chunk_size: usize) -> usize;
+        pub fn density_hip_encode_sealed(algo: i32, input: *const u8, input_size: usize, output: *mut u8, output_size: usize, chunk_size: usize) -> usize;
+        pub fn density_hip_checksum_device(d_data: *const core::ffi::c_void, size: usize, chunk_size: usize, d_sums: *mut u32, stream: *mut core::ffi::c_void) -> i32;
+        pub fn density_hip_seal_device(d_input: *const core::ffi::c_void, input_size: usize, d_container: *mut core::ffi::c_void, container_capacity: usize,
+                                       header: *const DensityHipHeader, stream: *mut core::ffi::c_void, header_out: *mut DensityHipHeader) -> i32;
+    }
+}
+
 pub mod errors {
     pub mod encode_error { #[derive(Debug)] pub struct EncodeError {} }
     pub mod decode_error { #[derive(Debug)] pub struct DecodeError {} }

@@ -13,7 +13,7 @@ ALGO_IDS = {"chameleon": 0, "cheetah": 1, "lion": 2}
 ALGO_NAMES = {v: k for k, v in ALGO_IDS.items()}
 DEFAULT_CHUNK = 1 << 20
 
-OK, ERR_ARGUMENT, ERR_CAPACITY, ERR_FORMAT, ERR_RUNTIME, ERR_UNSUPPORTED = range(6)
+OK, ERR_ARGUMENT, ERR_CAPACITY, ERR_FORMAT, ERR_RUNTIME, ERR_UNSUPPORTED, ERR_CHECKSUM = range(7)
 
 
 class Header(ctypes.Structure):
@@ -63,6 +63,11 @@ SYMBOLS.update({
     "density_hip_encode": (_SZ, [_I, _VP, _SZ, _VP, _SZ, _SZ]),
     "density_hip_decode": (_SZ, [_VP, _SZ, _VP, _SZ]),
     "density_hip_decoded_size": (_SZ, [_VP, _SZ]),
+    "density_hip_encode_sealed": (_SZ, [_I, _VP, _SZ, _VP, _SZ, _SZ]),
+    "density_hip_checksum32": (ctypes.c_uint32, [_VP, _SZ]),
+    "density_hip_seal_overhead": (_SZ, [_SZ, _SZ]),
+    "density_hip_checksum_device": (_I, [_VP, _SZ, _SZ, _VP, _VP]),
+    "density_hip_seal_device": (_I, [_VP, _SZ, _VP, _SZ, ctypes.POINTER(Header), _VP, ctypes.POINTER(Header)]),
     "density_hip_encode_workspace_size": (_SZ, [_I, _SZ, _SZ]),
     "density_hip_decode_workspace_size": (_SZ, [ctypes.c_uint32]),
     "density_hip_decode_workspace_size_for": (_SZ, [_I, _SZ, _SZ]),

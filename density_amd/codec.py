@@ -24,6 +24,10 @@ class DecodeError(Exception):
     """errors/decode_error.rs"""
 
 
+class ChecksumError(DecodeError):
+    """A sealed container (include/density_hip.h: DENSITY_HIP_FLAG_CHECKSUM) decoded without a format error, but not to the bytes that were sealed."""
+
+
 def _c_contiguous(ai):
     """True if an __array_interface__ describes one C-ordered run of bytes (strides None, or the C strides of its shape)."""
     strides = ai.get("strides")

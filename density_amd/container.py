@@ -6,7 +6,7 @@ data_ptr()) and a HIP stream handle and enqueue kernels only.
 import ctypes
 
 from . import _lib
-from .codec import DecodeError, EncodeError, _ro, _rw
+from .codec import ChecksumError, DecodeError, EncodeError, _ro, _rw
 
 
 def container_bound(algo, input_size, chunk_size=0):
@@ -32,7 +32,7 @@ def decode(container, output):
     oa, cap, k2 = _rw(output)
     r = _lib.lib().density_hip_decode(ia, n, oa, cap)
     if r == 0 and _lib.last_error():          # 0 with no error == a valid, empty container
-        raise DecodeError(_lib.last_error())
+        raise (ChecksumError if _lib.last_error().startswith("checksum") else DecodeError)(_lib.last_error())
     return r
 
 
@@ -44,6 +44,7 @@ def parse_header(raw32):
 FLAG_BLOCK_INDEX = 1
 FLAG_SLOTTED = 2
 FLAG_PAGED = 4
+FLAG_CHECKSUM = 8
 PAGE_BYTES = 65536
 
 
@@ -100,8 +101,55 @@ def chunk_payloads(container):
 
 
 def _check(rc, exc):
+    if rc == _lib.ERR_CHECKSUM:
+        raise ChecksumError(f"density_hip error {rc}: {_lib.last_error()}")
     if rc != _lib.OK:
         raise exc(f"density_hip error {rc}: {_lib.last_error()}")
+
+
+def checksum32(data):
+    """The content checksum C of a sealed container's chunk (include/density_hip.h: DENSITY_HIP_FLAG_CHECKSUM), computed on the host."""
+    ia, n, k = _ro(data)
+    return int(_lib.lib().density_hip_checksum32(ia, n))
+
+
+def seal_overhead(input_size, chunk_size=0):
+    """Upper bound of what sealing adds to any container_bound*()."""
+    return int(_lib.lib().density_hip_seal_overhead(input_size, chunk_size))
+
+
+def chunk_checksums(container):
+    """The trailer of a host-resident sealed container, one checksum per chunk, or None where the container is not sealed."""
+    b = bytes(container)
+    h = parse_header(b)
+    if not (h.flags & FLAG_CHECKSUM):
+        return None
+    at = h.container_len - (4 * h.n_chunks + 15) // 16 * 16
+    return [int.from_bytes(b[at + 4 * i:at + 4 * i + 4], "little") for i in range(h.n_chunks)]
+
+
+def encode_sealed(algo, input, output, chunk_size=0):
+    """As encode, sealed on the device before the copy down: the packed container with its trailer of content checksums."""
+    ia, n, k1 = _ro(input)
+    oa, cap, k2 = _rw(output)
+    r = _lib.lib().density_hip_encode_sealed(_lib.ALGO_IDS[algo], ia, n, oa, cap, chunk_size)
+    if r == 0:
+        raise EncodeError(_lib.last_error())
+    return r
+
+
+def checksum_device(d_data, n, chunk_size, d_sums, stream=0):
+    """Enqueue the checksums of every chunk_size bytes of device memory into d_sums (u32 per chunk, cleared by the call)."""
+    _check(_lib.lib().density_hip_checksum_device(d_data, n, chunk_size, d_sums, stream), EncodeError)
+
+
+def seal_device(d_in, n, d_container, cap, header=None, stream=0, want_header=True):
+    """Seal, in place, the container an encode_device* call has just written for d_in.  Returns the sealed header (synchronises) or None."""
+    hdr = _lib.Header() if want_header else None
+    rc = _lib.lib().density_hip_seal_device(d_in, n, d_container, cap, ctypes.byref(header) if header is not None else None, stream,
+                                            ctypes.byref(hdr) if want_header else None)
+    _check(rc, EncodeError)
+    return hdr
 
 
 def encode_device(algo, d_in, n, d_out, cap, chunk_size=0, stream=0, workspace=(0, 0), want_header=True):

@@ -137,14 +137,16 @@ int check_header(const density_hip_header_t& h, size_t container_size) {
     if (h.magic != DENSITY_HIP_MAGIC || h.version != 1 || !valid_algo(h.algo)) return DENSITY_HIP_ERR_FORMAT;
     if (!valid_chunk(h.chunk_size)) return DENSITY_HIP_ERR_FORMAT;
     if (h.n_chunks != chunk_count(h.total_len, h.chunk_size)) return DENSITY_HIP_ERR_FORMAT;
-    if (h.flags & ~(DENSITY_HIP_FLAG_BLOCK_INDEX | DENSITY_HIP_FLAG_SLOTTED | DENSITY_HIP_FLAG_PAGED)) return DENSITY_HIP_ERR_FORMAT;
+    if (h.flags & ~(DENSITY_HIP_FLAG_BLOCK_INDEX | DENSITY_HIP_FLAG_SLOTTED | DENSITY_HIP_FLAG_PAGED | DENSITY_HIP_FLAG_CHECKSUM)) return DENSITY_HIP_ERR_FORMAT;
+    const size_t trailer = header_trailer(h);                                      // a sealed container ends in its trailer: the form's own rules hold for what lies in front of it
     if (h.flags & DENSITY_HIP_FLAG_PAGED) {                                        // pages: Chameleon with its block index, whole pages behind the directory
         if (h.algo != DENSITY_HIP_CHAMELEON || (h.flags & (DENSITY_HIP_FLAG_BLOCK_INDEX | DENSITY_HIP_FLAG_SLOTTED)) != DENSITY_HIP_FLAG_BLOCK_INDEX) return DENSITY_HIP_ERR_FORMAT;
         const size_t pb = paged_pages_base(h.n_chunks, h.total_len, h.chunk_size);
-        if (h.container_len > container_size || h.container_len < pb || (h.container_len - pb) % kPageBytes != 0 || h.container_len - pb >= (1ull << 32)) return DENSITY_HIP_ERR_FORMAT;
+        if (h.container_len > container_size || h.container_len < pb + trailer) return DENSITY_HIP_ERR_FORMAT;
+        if ((h.container_len - trailer - pb) % kPageBytes != 0 || h.container_len - trailer - pb >= (1ull << 32)) return DENSITY_HIP_ERR_FORMAT;
         return DENSITY_HIP_OK;
     }
-    if (h.container_len > container_size || h.container_len < payload_base(h.n_chunks, h.total_len, h.flags & DENSITY_HIP_FLAG_BLOCK_INDEX)) return DENSITY_HIP_ERR_FORMAT;
+    if (h.container_len > container_size || h.container_len < payload_base(h.n_chunks, h.total_len, h.flags & DENSITY_HIP_FLAG_BLOCK_INDEX) + trailer) return DENSITY_HIP_ERR_FORMAT;
     return DENSITY_HIP_OK;
 }
 
@@ -273,6 +275,9 @@ int run_decode_container(DeviceCtx* c, const uint8_t* d_in, size_t container_siz
     hipError_t e = hipMemsetAsync(d_err, 0, sizeof(uint32_t), s);
     const bool with_index = h.flags & DENSITY_HIP_FLAG_BLOCK_INDEX;
     const uint8_t* d_index = with_index ? d_in + index_base(h.n_chunks) : nullptr;
+    // a sealed container's trailer is not payload: the streams and pages end in front of it
+    const size_t trailer = header_trailer(h), body_len = h.container_len - trailer;
+    if (trailer) container_size = body_len;
     if (h.flags & DENSITY_HIP_FLAG_PAGED) {
         // the pages are read where they lie: the rotation decoder turns stream positions into page offsets through the chunk's directory
         const size_t dir_base = paged_dir_base(h.n_chunks, h.total_len), pages_base = paged_pages_base(h.n_chunks, h.total_len, h.chunk_size);
@@ -283,7 +288,7 @@ int run_decode_container(DeviceCtx* c, const uint8_t* d_in, size_t container_siz
         prof.mark("layout_decode");
         if (e == hipSuccess) e = launch_rotor_decode_paged(d_in + pages_base, d_offsets, d_sizes, h.n_chunks, d_out, h.chunk_size, h.total_len, d_index,
                                                          reinterpret_cast<const uint32_t*>(d_in + dir_base), page_dir_words(paged_pages_per_chunk(h.chunk_size)),
-                                                         (uint32_t)((h.container_len - pages_base) / kPageBytes), d_zmap, d_produced, d_err, s);
+                                                         (uint32_t)((body_len - pages_base) / kPageBytes), d_zmap, d_produced, d_err, s);
         prof.mark(decode_kernel_name(h.algo));
     } else {
         if (e == hipSuccess) e = launch_layout_decode(d_in, container_size, h.n_chunks, payload_base(h.n_chunks, h.total_len, with_index), d_sizes, d_offsets, d_err, s,
@@ -293,12 +298,19 @@ int run_decode_container(DeviceCtx* c, const uint8_t* d_in, size_t container_siz
                                               p.pass(ws, ws_size));
         prof.mark(decode_kernel_name(h.algo));
     }
+    if (trailer) {
+        // sealed: the sum of what was just decoded against the trailer, on the device (the decoders' per-chunk counts are not needed any more: their
+        // words hold the sums).  Whatever a damaged stream decoded to lies inside the output: the decoders write nothing past it.
+        if (e == hipSuccess) e = launch_checksum(d_out, h.total_len, h.chunk_size, h.n_chunks, reinterpret_cast<uint32_t*>(d_produced), d_in + body_len, d_err, s);
+        prof.mark("checksum_verify");
+    }
     if (e != hipSuccess) { set_error("kernel launch (decode)", e); return DENSITY_HIP_ERR_RUNTIME; }
     if (decoded_out) {
         uint32_t h_err = 0;
         e = read_back(s, d_err, &h_err);
         if (e != hipSuccess) { set_error("decode (device)", e); return DENSITY_HIP_ERR_RUNTIME; }
-        if (h_err) { set_error("malformed or truncated container payload"); *decoded_out = 0; return DENSITY_HIP_ERR_FORMAT; }
+        if (h_err & ~kErrChecksum) { set_error("malformed or truncated container payload"); *decoded_out = 0; return DENSITY_HIP_ERR_FORMAT; }
+        if (h_err) { set_error("checksum mismatch: the container decodes, but not to the bytes that were sealed"); *decoded_out = 0; return DENSITY_HIP_ERR_CHECKSUM; }
         *decoded_out = h.total_len;
     }
     return DENSITY_HIP_OK;
@@ -313,7 +325,13 @@ int run_pack_container(DeviceCtx* c, const uint8_t* d_in, size_t container_size,
     uint64_t* d_sizes64 = p.produced(ws);                                              // (the u64 sizes the layout kernel wants)
     const bool with_index = h.flags & DENSITY_HIP_FLAG_BLOCK_INDEX;
     const uint64_t pbase = payload_base(h.n_chunks, h.total_len, with_index);
-    if (cap < container_bound(h.algo, h.total_len, h.chunk_size)) { set_error("output capacity below density_hip_container_bound()"); return DENSITY_HIP_ERR_CAPACITY; }
+    // a sealed container: its trailer (not payload: the streams end in front of it) moves behind the packed streams, once the layout kernel has said where they end
+    const size_t trailer = header_trailer(h), body_len = h.container_len - trailer;
+    if (trailer) container_size = body_len;
+    if (cap < container_bound(h.algo, h.total_len, h.chunk_size) + (trailer ? seal_overhead(h.n_chunks) : 0)) {
+        set_error(trailer ? "output capacity below density_hip_container_bound() + density_hip_seal_overhead()" : "output capacity below density_hip_container_bound()");
+        return DENSITY_HIP_ERR_CAPACITY;
+    }
     Profiler prof(c, s);
     hipError_t e = hipMemsetAsync(d_err, 0, sizeof(uint32_t), s);
     const uint64_t stride = (h.flags & DENSITY_HIP_FLAG_SLOTTED) ? slot_stride(h.algo, h.chunk_size) : 0;
@@ -321,22 +339,53 @@ int run_pack_container(DeviceCtx* c, const uint8_t* d_in, size_t container_size,
     if (e == hipSuccess) e = launch_layout_decode(d_in, container_size, h.n_chunks, pbase, d_sizes64, d_offsets, d_err, s, stride);
     if (e == hipSuccess) e = hipMemcpyAsync(d_out + sizeof(h), d_in + sizeof(h), pbase - sizeof(h), hipMemcpyDeviceToDevice, s);   // size table + block index
     density_hip_header_t out_h = h;
-    out_h.flags = h.flags & ~DENSITY_HIP_FLAG_SLOTTED;
+    out_h.flags = h.flags & ~(DENSITY_HIP_FLAG_SLOTTED | DENSITY_HIP_FLAG_CHECKSUM);
     out_h.container_len = 0;
     if (e == hipSuccess) e = launch_layout_encode(d_sizes64, h.n_chunks, out_h, pbase, d_out, cap, d_sizes /* packed offsets */, d_err, s);
     prof.mark("layout_encode");
     if (e == hipSuccess) {
         if (stride) e = launch_compact(d_in + pbase, stride, d_sizes64, d_sizes, h.n_chunks, d_out, d_err, s);
-        else if (h.container_len > cap || h.container_len < pbase) { set_error("output capacity below the container's length"); return DENSITY_HIP_ERR_CAPACITY; }
-        else e = hipMemcpyAsync(d_out + pbase, d_in + pbase, h.container_len - pbase, hipMemcpyDeviceToDevice, s);   // (already packed: its own bytes, no more)
+        else if (body_len > cap || body_len < pbase) { set_error("output capacity below the container's length"); return DENSITY_HIP_ERR_CAPACITY; }
+        else e = hipMemcpyAsync(d_out + pbase, d_in + pbase, body_len - pbase, hipMemcpyDeviceToDevice, s);   // (already packed: its own bytes, no more)
     }
     prof.mark("compact");
+    if (trailer) {
+        if (e == hipSuccess) e = launch_move_trailer(d_in + body_len, d_out, cap, h.n_chunks, d_err, s);
+        prof.mark("move_trailer");
+    }
     if (e != hipSuccess) { set_error("kernel launch (pack)", e); return DENSITY_HIP_ERR_RUNTIME; }
     if (header_out) {
         uint32_t h_err = 0;
         e = read_back(s, d_err, &h_err, header_out, d_out, sizeof(*header_out));
         if (e != hipSuccess) { set_error("pack (device)", e); return DENSITY_HIP_ERR_RUNTIME; }
         if (h_err) { set_error("malformed slotted container"); return DENSITY_HIP_ERR_FORMAT; }
+    }
+    return DENSITY_HIP_OK;
+}
+
+// The seal of the container just written for d_in, in place: every chunk of the INPUT summed (checksum.hip), the trailer behind the container, the flag
+// and the new length in its header.  Where the container ends, and how the input was cut, is read from the header on the device, so that nothing here
+// waits for the encoder; the caller's copy of the header only lets the call refuse at once what the device would refuse.
+int run_seal_container(DeviceCtx* c, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, const density_hip_header_t* header, uint8_t* ws, hipStream_t s,
+                       density_hip_header_t* header_out) {
+    if (header) {
+        if (check_header(*header, cap) != DENSITY_HIP_OK) { set_error("seal: bad container header"); return DENSITY_HIP_ERR_ARGUMENT; }
+        if (header->flags & DENSITY_HIP_FLAG_CHECKSUM) { set_error("seal: the container is sealed already"); return DENSITY_HIP_ERR_ARGUMENT; }
+        if (header->total_len != n) { set_error("seal: input_size is not the container's total_len"); return DENSITY_HIP_ERR_ARGUMENT; }
+        if (align_up(header->container_len, 16) + trailer_bytes(header->n_chunks) > cap) { set_error("seal: the capacity does not hold the trailer (density_hip_seal_overhead())"); return DENSITY_HIP_ERR_CAPACITY; }
+    }
+    const SealPlan p = plan_seal(n);
+    Profiler prof(c, s);
+    hipError_t e = hipMemsetAsync(p.err(ws), 0, sizeof(uint32_t), s);
+    if (e == hipSuccess) e = launch_seal(d_in, n, d_out, cap, p.geom(ws), p.acc(ws), p.err(ws), s);
+    prof.mark("checksum_seal");
+    if (e != hipSuccess) { set_error("kernel launch (seal)", e); return DENSITY_HIP_ERR_RUNTIME; }
+    if (header_out) {
+        uint32_t h_err = 0;
+        e = read_back(s, p.err(ws), &h_err, header_out, d_out, sizeof(*header_out));
+        if (e != hipSuccess) { set_error("seal (device)", e); return DENSITY_HIP_ERR_RUNTIME; }
+        if (h_err & 1u) { set_error("seal: not this input's unsealed container (sealed already, or input_size is not its total_len)"); return DENSITY_HIP_ERR_ARGUMENT; }
+        if (h_err) { set_error("seal: the capacity does not hold the trailer (density_hip_seal_overhead())"); return DENSITY_HIP_ERR_CAPACITY; }
     }
     return DENSITY_HIP_OK;
 }
@@ -452,6 +501,30 @@ int density_hip_decode_device(const void* d_container, size_t container_size, co
     uint8_t* ws = nullptr;
     if (const int rc = resolve_workspace(c, d_workspace, workspace_size, dp.total, dp.total_with_passes, &ws, &workspace_size)) return rc;
     return run_decode_container(c, (const uint8_t*)d_container, container_size, h, (uint8_t*)d_output, output_capacity, ws, s, decoded_size_out, workspace_size);
+}
+
+int density_hip_checksum_device(const void* d_data, size_t size, size_t chunk_size, uint32_t* d_sums, void* stream) {
+    g_last_error.clear();
+    const size_t n_chunks = valid_chunk(chunk_size) ? chunk_count(size, chunk_size) : 0;
+    if (!valid_chunk(chunk_size) || n_chunks > 0xffffffffull || (size && (!d_data || !d_sums)) || (uintptr_t)d_sums % 4 != 0) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return DENSITY_HIP_ERR_RUNTIME;
+    const hipError_t e = launch_checksum((const uint8_t*)d_data, size, (uint32_t)chunk_size, (uint32_t)n_chunks, d_sums, nullptr, nullptr, stream ? (hipStream_t)stream : c->stream);
+    if (e != hipSuccess) { set_error("kernel launch (checksum)", e); return DENSITY_HIP_ERR_RUNTIME; }
+    return DENSITY_HIP_OK;
+}
+
+int density_hip_seal_device(const void* d_input, size_t input_size, void* d_container, size_t container_capacity, const density_hip_header_t* header,
+                            void* stream, density_hip_header_t* header_out) {
+    g_last_error.clear();
+    if (!d_container || container_capacity < sizeof(density_hip_header_t) || (!d_input && input_size)) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return DENSITY_HIP_ERR_RUNTIME;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const size_t need = plan_seal(input_size).total;
+    uint8_t* ws = nullptr;
+    if (const int rc = resolve_workspace(c, nullptr, 0, need, need, &ws)) return rc;
+    return run_seal_container(c, (const uint8_t*)d_input, input_size, (uint8_t*)d_container, container_capacity, header, ws, stream ? (hipStream_t)stream : c->stream, header_out);
 }
 
 uint64_t density_hip_decode_pass_count(void) { return g_pass_decodes; }

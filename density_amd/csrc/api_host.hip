@@ -62,7 +62,9 @@ size_t decode_container_pipelined(DeviceCtx* c, const uint8_t* container, const 
     *handled = false;
     const uint32_t nc = h.n_chunks;
     const size_t chunk = h.chunk_size, total = h.total_len;
-    if (!pipe_wanted(h.algo, total, chunk, nc) || (h.flags & (DENSITY_HIP_FLAG_SLOTTED | DENSITY_HIP_FLAG_PAGED))) return 0;   // (slices follow the PACKED layout: a paged blob's streams lie in pages — the staged call reads them in place)
+    // (slices follow the PACKED layout: a paged blob's streams lie in pages — the staged call reads them in place; a sealed container is verified
+    // against its trailer by the staged call, whole)
+    if (!pipe_wanted(h.algo, total, chunk, nc) || (h.flags & (DENSITY_HIP_FLAG_SLOTTED | DENSITY_HIP_FLAG_PAGED | DENSITY_HIP_FLAG_CHECKSUM))) return 0;
     PinnedInPlace pin_in(container, h.container_len), pin_out(output, total);
     if (!pin_in || !pin_out) return 0;
     const bool with_index = h.flags & DENSITY_HIP_FLAG_BLOCK_INDEX;
@@ -193,6 +195,22 @@ size_t encode_container_pipelined(DeviceCtx* c, int algo, const uint8_t* input, 
     return (size_t)end;
 }
 
+// the staged call: the input up whole, the packed container made on the device — and sealed there where asked — and down whole (ctx locked)
+size_t encode_container_staged(DeviceCtx* c, int algo, const uint8_t* input, size_t input_size, uint8_t* output, size_t output_size, size_t chunk_size, bool seal) {
+    const size_t packed = container_bound(algo, input_size, chunk_size), bound = packed + (seal ? seal_overhead(chunk_count(input_size, chunk_size)) : 0);
+    const size_t ws_bytes = std::max(plan_encode(algo, input_size, chunk_size).total, seal ? plan_seal(input_size).total : 0);
+    hipError_t e = ensure_staging(c, input_size ? input_size : 1, bound, ws_bytes);
+    if (e == hipSuccess && input_size) e = copy_host_side_pinned(c->stage_in.p, input, input_size, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) { set_error("staging (H2D)", e); return 0; }
+    density_hip_header_t h;
+    if (run_encode_container(c, algo, (const uint8_t*)c->stage_in.p, input_size, (uint8_t*)c->stage_out.p, packed, chunk_size, (uint8_t*)c->work.p, c->stream, &h) != DENSITY_HIP_OK) return 0;
+    if (seal && run_seal_container(c, (const uint8_t*)c->stage_in.p, input_size, (uint8_t*)c->stage_out.p, bound, &h, (uint8_t*)c->work.p, c->stream, &h) != DENSITY_HIP_OK) return 0;
+    if (h.container_len > output_size) { set_error("output buffer too small"); return 0; }
+    e = copy_host_side_pinned(output, c->stage_out.p, h.container_len, hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) { set_error("staging (D2H)", e); return 0; }
+    return (size_t)h.container_len;
+}
+
 }  // namespace
 }  // namespace api
 }  // namespace density
@@ -213,16 +231,16 @@ size_t density_hip_encode(int algo, const uint8_t* input, size_t input_size, uin
         const size_t r = encode_container_pipelined(c, algo, input, input_size, output, output_size, chunk_size, &handled);
         if (handled) return r;
     }
-    const size_t bound = container_bound(algo, input_size, chunk_size);
-    hipError_t e = ensure_staging(c, input_size ? input_size : 1, bound, plan_encode(algo, input_size, chunk_size).total);
-    if (e == hipSuccess && input_size) e = copy_host_side_pinned(c->stage_in.p, input, input_size, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) { set_error("staging (H2D)", e); return 0; }
-    density_hip_header_t h;
-    if (run_encode_container(c, algo, (const uint8_t*)c->stage_in.p, input_size, (uint8_t*)c->stage_out.p, bound, chunk_size, (uint8_t*)c->work.p, c->stream, &h) != DENSITY_HIP_OK) return 0;
-    if (h.container_len > output_size) { set_error("output buffer too small"); return 0; }
-    e = copy_host_side_pinned(output, c->stage_out.p, h.container_len, hipMemcpyDeviceToHost, c->stream);
-    if (e != hipSuccess) { set_error("staging (D2H)", e); return 0; }
-    return (size_t)h.container_len;
+    return encode_container_staged(c, algo, input, input_size, output, output_size, chunk_size, false);
+}
+
+size_t density_hip_encode_sealed(int algo, const uint8_t* input, size_t input_size, uint8_t* output, size_t output_size, size_t chunk_size) {
+    g_last_error.clear();
+    if (!take_geometry(algo, input_size, &chunk_size) || (!input && input_size) || !output) { set_error("bad argument"); return 0; }
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return encode_container_staged(c, algo, input, input_size, output, output_size, chunk_size, true);
 }
 
 size_t density_hip_decoded_size(const uint8_t* container, size_t container_size) {

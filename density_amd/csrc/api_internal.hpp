@@ -106,6 +106,19 @@ inline bool paged_eligible(int algo, size_t n, size_t chunk) {
 }
 size_t container_bound_paged(int algo, size_t n, size_t chunk);
 inline size_t slot_stride(int algo, size_t chunk) { return align_up(safe_size(algo, chunk), kAlign); }
+// sealed container (DENSITY_HIP_FLAG_CHECKSUM): the trailer of a word per chunk at the container's end, and what sealing can add to a bound (the gap in front of it too)
+inline size_t trailer_bytes(size_t n_chunks) { return align_up(4 * n_chunks, 16); }
+inline size_t header_trailer(const density_hip_header_t& h) { return (h.flags & DENSITY_HIP_FLAG_CHECKSUM) ? trailer_bytes(h.n_chunks) : 0; }
+inline size_t seal_overhead(size_t n_chunks) { return 16 + trailer_bytes(n_chunks); }
+// the scratch of a seal in a workspace: the error word, the geometry the device reads from the container's header, a word per chunk (of which an
+// input of n bytes has at most one per 256 bytes)
+struct SealPlan {
+    size_t total;
+    uint32_t* err(uint8_t* ws) const { return reinterpret_cast<uint32_t*>(ws); }
+    uint32_t* geom(uint8_t* ws) const { return reinterpret_cast<uint32_t*>(ws + 64); }
+    uint32_t* acc(uint8_t* ws) const { return reinterpret_cast<uint32_t*>(ws + kAlign); }
+};
+inline SealPlan plan_seal(size_t n) { return SealPlan{kAlign + align_up(4 * ((n + 255) / 256) + 4, kAlign)}; }
 
 struct Buffer {
     void* p = nullptr;
@@ -334,6 +347,9 @@ int run_encode_container(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, 
                          uint8_t* ws, hipStream_t s, density_hip_header_t* header_out, Form form = Form::Packed);
 int run_decode_container(DeviceCtx* c, const uint8_t* d_in, size_t container_size, const density_hip_header_t& h, uint8_t* d_out,
                          size_t cap, uint8_t* ws, hipStream_t s, size_t* decoded_out, size_t ws_size = 0);
+// the seal of the container just encoded for d_in (`ws`: plan_seal(n).total bytes); `header`: the caller's copy of its header, or nullptr
+int run_seal_container(DeviceCtx* c, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, const density_hip_header_t* header, uint8_t* ws, hipStream_t s,
+                       density_hip_header_t* header_out);
 // ... of one reference stream (api_stream.hip)
 int run_stream_encode(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, uint8_t* ws, hipStream_t s, size_t* size_out);
 int run_stream_decode(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, uint8_t* ws, hipStream_t s, size_t* size_out);

@@ -1,0 +1,187 @@
+// checksum.hip — content checksums for gfx950: C (checksum.hpp) of every chunk of a device buffer, and the small kernels that seal a container
+// with them (a trailer of one word per chunk behind the container: include/density_hip.h, DENSITY_HIP_FLAG_CHECKSUM), carry a trailer along when a
+// slotted container is packed, and hold a decoder's output against one.
+//
+// The sum kernel only reads: a chunk is cut into tiles of 32 KiB, a work-group takes tiles in a grid-stride loop, every lane has eight 16-byte loads
+// in flight, mixes each word with its index IN THE CHUNK (not its address: the buffer may start anywhere), and the work-group adds its partial sum
+// to the chunk's accumulator with one global atomic.  The sum commutes, so neither the tiles nor the atomics need an order.  A second, tiny kernel
+// turns the accumulators into C = fmix32(S + L), or compares them with a trailer.
+#include "checksum.hpp"
+#include "common.hpp"
+#include "kernels.hpp"
+
+namespace density {
+
+namespace {
+
+constexpr uint32_t kSumThreads = 256, kSumLoads = 8;
+constexpr uint32_t kSumTile = kSumThreads * 16u * kSumLoads;   // 32 KiB per work-group and trip
+constexpr uint32_t kSumMaxGroups = 256u * 8u;                  // eight work-groups a CU; what is left is taken in the grid-stride loop
+constexpr uint32_t kSmallThreads = 1024;
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ uint64_t align16(uint64_t v) { return (v + 15ull) & ~15ull; }
+__device__ __forceinline__ uint64_t ld64u(const uint8_t* p) { return *reinterpret_cast<const u64_u*>(p); }
+__device__ __forceinline__ void st64u(uint8_t* p, uint64_t v) { *reinterpret_cast<u64_u*>(p) = v; }
+
+// 16 bytes from any address: one global_load_dwordx4 (gfx950 global memory takes unaligned accesses, as for the dwords of common.hpp)
+__device__ __forceinline__ u32x4 load16(const uint8_t* p) {
+    u32x4 v;
+    __builtin_memcpy(&v, p, 16);
+    return v;
+}
+
+// bytes of chunk `c` of a buffer of `size` bytes cut every `chunk` bytes
+__device__ __forceinline__ uint32_t chunk_len(uint64_t size, uint32_t chunk, uint32_t c) {
+    const uint64_t begin = (uint64_t)c * chunk;
+    return size - begin < chunk ? (uint32_t)(size - begin) : chunk;
+}
+
+// d_geom (nullable; the asynchronous seal, whose geometry only the device knows): {chunk size, chunks} as seal_prepare_kernel took them from the
+// container's header, {.., 0} where that header is not to be followed
+__global__ __launch_bounds__(kSumThreads) void checksum_tiles_kernel(const uint8_t* __restrict__ data, uint64_t size, uint32_t chunk, uint32_t n_chunks,
+                                                                     const uint32_t* __restrict__ d_geom, uint32_t* __restrict__ acc) {
+    __shared__ uint32_t part[kSumThreads / 64];
+    if (d_geom) { chunk = d_geom[0]; n_chunks = d_geom[1]; }
+    if (n_chunks == 0) return;
+    const uint32_t tiles = (chunk + kSumTile - 1) / kSumTile;
+    const uint64_t units = (uint64_t)n_chunks * tiles;
+    for (uint64_t u = blockIdx.x; u < units; u += gridDim.x) {
+        const uint32_t c = (uint32_t)(u / tiles), t0 = (uint32_t)(u % tiles) * kSumTile;
+        const uint32_t len = chunk_len(size, chunk, c);
+        if (t0 >= len) continue;                                             // (the ragged last chunk: the same for the whole work-group)
+        const uint8_t* p = data + (uint64_t)c * chunk;
+        u32x4 v[kSumLoads];
+#pragma unroll
+        for (uint32_t j = 0; j < kSumLoads; ++j) {
+            const uint32_t off = t0 + (j * kSumThreads + threadIdx.x) * 16u;
+            v[j] = (off < len && len - off >= 16u) ? load16(p + off) : u32x4{0u, 0u, 0u, 0u};
+        }
+        uint32_t sum = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < kSumLoads; ++j) {
+            const uint32_t off = t0 + (j * kSumThreads + threadIdx.x) * 16u, i = off / 4u;
+            if (off >= len) continue;
+            if (len - off >= 16u) {
+                sum += sum_term(v[j].x, i) + sum_term(v[j].y, i + 1u) + sum_term(v[j].z, i + 2u) + sum_term(v[j].w, i + 3u);
+            } else {                                                         // the chunk's last 1..15 bytes: whole words, then one padded with zeros
+                const uint32_t rem = len - off;
+                for (uint32_t k = 0; k < rem; k += 4u) {
+                    uint32_t w = 0;
+                    for (uint32_t b = 0; b < 4u && k + b < rem; ++b) w |= (uint32_t)p[off + k + b] << (8u * b);
+                    sum += sum_term(w, i + k / 4u);
+                }
+            }
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
+        if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = sum;
+        __syncthreads();
+        if (threadIdx.x == 0) atomicAdd(acc + c, part[0] + part[1] + part[2] + part[3]);
+        __syncthreads();                                                     // (part is written again in the next trip)
+    }
+}
+
+// acc[c] = S of chunk c -> C = fmix32(S + L); with `expect` (n_chunks words at any alignment: a trailer) nothing is written but *err, where they differ
+__global__ __launch_bounds__(256) void checksum_finish_kernel(uint32_t* __restrict__ acc, uint64_t size, uint32_t chunk, uint32_t n_chunks,
+                                                              const uint8_t* __restrict__ expect, uint32_t* __restrict__ err) {
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= n_chunks) return;
+    const uint32_t sum = fmix32(acc[c] + chunk_len(size, chunk, c));
+    if (!expect) acc[c] = sum;
+    else if (sum != ld32u(expect + 4ull * c)) atomicOr(err, kErrChecksum);
+}
+
+// The seal, first step: the header the encoder left on the device says where the trailer goes.  A header that is not this input's (or is sealed
+// already) raises bit 1 of *err, a capacity that does not hold the trailer bit 2; either way d_geom says "no chunks" and nothing more happens.
+// Otherwise the accumulators are cleared for the sum kernel.  One work-group.
+__global__ __launch_bounds__(kSmallThreads) void seal_prepare_kernel(const uint8_t* __restrict__ container, uint64_t capacity, uint64_t input_size,
+                                                                     uint32_t* __restrict__ d_geom, uint32_t* __restrict__ acc, uint32_t* __restrict__ err) {
+    const uint32_t magic = ld32u(container), version = container[5], flags = ld16u(container + 6), chunk = ld32u(container + 8), n = ld32u(container + 12);
+    const uint64_t total = ld64u(container + 16), len = ld64u(container + 24);
+    const bool bad = magic != DENSITY_HIP_MAGIC || version != 1 || chunk < 256u || chunk % 256u != 0 || (flags & DENSITY_HIP_FLAG_CHECKSUM) || total != input_size ||
+                     n != (total + chunk - 1) / chunk || len < sizeof(density_hip_header_t) || len > capacity;
+    const bool fits = !bad && align16(len) + align16(4ull * n) <= capacity;
+    if (threadIdx.x == 0) {
+        d_geom[0] = chunk;
+        d_geom[1] = fits ? n : 0u;
+        d_geom[2] = fits ? 1u : 0u;
+        if (bad) atomicOr(err, 1u);
+        else if (!fits) atomicOr(err, 2u);
+    }
+    if (fits) for (uint32_t i = threadIdx.x; i < n; i += kSmallThreads) acc[i] = 0u;
+}
+
+// ... last step: the trailer behind the container (the gap in front of it and its own padding are zeros: they are wire bytes now), then the flag
+// and the new length.  The container may lie at any address.
+__global__ __launch_bounds__(kSmallThreads) void seal_finish_kernel(uint8_t* __restrict__ container, uint64_t input_size, const uint32_t* __restrict__ d_geom,
+                                                                    const uint32_t* __restrict__ acc) {
+    if (!d_geom[2]) return;
+    const uint32_t chunk = d_geom[0], n = d_geom[1];
+    const uint64_t len = ld64u(container + 24), at = align16(len), bytes = align16(4ull * n);
+    const uint32_t flags = ld16u(container + 6);
+    __syncthreads();                                                         // (everyone has the old length before thread 0 replaces it)
+    for (uint32_t i = threadIdx.x; i < n; i += kSmallThreads) st32u(container + at + 4ull * i, fmix32(acc[i] + chunk_len(input_size, chunk, i)));
+    if (threadIdx.x < at - len) container[len + threadIdx.x] = 0;
+    if (threadIdx.x < bytes - 4ull * n) container[at + 4ull * n + threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+        st16u(container + 6, flags | DENSITY_HIP_FLAG_CHECKSUM);
+        st64u(container + 24, at + bytes);
+    }
+}
+
+// A trailer (n words at `src`) to its place behind the packed container the layout and gather kernels have just written into `dst`: nothing where
+// they raised *err, bit 2 where the capacity does not hold it.
+__global__ __launch_bounds__(kSmallThreads) void move_trailer_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, uint64_t capacity, uint32_t n,
+                                                                     uint32_t* __restrict__ err) {
+    if (*err) return;
+    const uint64_t len = ld64u(dst + 24), at = align16(len), bytes = align16(4ull * n);
+    const uint32_t flags = ld16u(dst + 6);
+    if (at + bytes > capacity) { if (threadIdx.x == 0) atomicOr(err, 2u); return; }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n; i += kSmallThreads) st32u(dst + at + 4ull * i, ld32u(src + 4ull * i));
+    if (threadIdx.x < at - len) dst[len + threadIdx.x] = 0;
+    if (threadIdx.x < bytes - 4ull * n) dst[at + 4ull * n + threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+        st16u(dst + 6, flags | DENSITY_HIP_FLAG_CHECKSUM);
+        st64u(dst + 24, at + bytes);
+    }
+}
+
+hipError_t launch_tiles(const uint8_t* d_data, uint64_t size, uint32_t chunk, uint32_t n_chunks, const uint32_t* d_geom, uint32_t* d_acc, hipStream_t stream) {
+    // with the geometry on the device alone, the tiles of the input as a whole stand in for the tiles of its chunks: the loop takes the rest
+    const uint64_t units = d_geom ? (size + kSumTile - 1) / kSumTile : (uint64_t)n_chunks * ((chunk + kSumTile - 1) / kSumTile);
+    const uint32_t groups = (uint32_t)(units < 1 ? 1 : units < kSumMaxGroups ? units : kSumMaxGroups);
+    hipLaunchKernelGGL(checksum_tiles_kernel, dim3(groups), dim3(kSumThreads), 0, stream, d_data, size, chunk, n_chunks, d_geom, d_acc);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_checksum(const uint8_t* d_data, uint64_t size, uint32_t chunk, uint32_t n_chunks, uint32_t* d_sums, const uint8_t* d_expect, uint32_t* d_err,
+                           hipStream_t stream) {
+    if (n_chunks == 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(d_sums, 0, 4ull * n_chunks, stream);
+    if (e == hipSuccess) e = launch_tiles(d_data, size, chunk, n_chunks, nullptr, d_sums, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(checksum_finish_kernel, dim3((n_chunks + 255u) / 256u), dim3(256), 0, stream, d_sums, size, chunk, n_chunks, d_expect, d_err);
+    return hipGetLastError();
+}
+
+hipError_t launch_seal(const uint8_t* d_in, uint64_t input_size, uint8_t* d_container, uint64_t capacity, uint32_t* d_geom, uint32_t* d_acc, uint32_t* d_err,
+                       hipStream_t stream) {
+    hipLaunchKernelGGL(seal_prepare_kernel, dim3(1), dim3(kSmallThreads), 0, stream, d_container, capacity, input_size, d_geom, d_acc, d_err);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = launch_tiles(d_in, input_size, 0, 0, d_geom, d_acc, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(seal_finish_kernel, dim3(1), dim3(kSmallThreads), 0, stream, d_container, input_size, d_geom, d_acc);
+    return hipGetLastError();
+}
+
+hipError_t launch_move_trailer(const uint8_t* d_trailer, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err, hipStream_t stream) {
+    hipLaunchKernelGGL(move_trailer_kernel, dim3(1), dim3(kSmallThreads), 0, stream, d_trailer, d_container, capacity, n_chunks, d_err);
+    return hipGetLastError();
+}
+
+}  // namespace density

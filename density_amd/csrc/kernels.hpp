@@ -177,4 +177,18 @@ hipError_t launch_compact(const uint8_t* d_slots, uint64_t slot_stride, const ui
 // LDS same-address ordering self-test (ascending lane order within one ds instruction). *d_fail != 0 on violation.
 hipError_t launch_selftest(uint32_t* d_fail, hipStream_t stream);
 
+// ---- checksum.hip (sealed containers, DENSITY_HIP_FLAG_CHECKSUM: the content checksum C of checksum.hpp, one word per chunk) ----
+constexpr uint32_t kErrChecksum = 0x100u;   // the bit of a decode's error word that says "decoded, but not what was sealed" (the codec kernels use bits 0..4)
+// C of every `chunk` bytes of d_data (any alignment) into d_sums[n_chunks] (4-byte aligned; cleared here, not by the caller).  With d_expect
+// (n_chunks words at any alignment: a trailer) d_sums is scratch and a difference raises kErrChecksum in *d_err instead.
+hipError_t launch_checksum(const uint8_t* d_data, uint64_t size, uint32_t chunk, uint32_t n_chunks, uint32_t* d_sums, const uint8_t* d_expect, uint32_t* d_err,
+                           hipStream_t stream);
+// Seals the container an encoder has just written for d_in, in place, from its header ON THE DEVICE: trailer, flag, new container_len.  d_geom: 4
+// words, d_acc: a word per chunk (at most one per 256 bytes of input) of scratch.  *d_err bit 1: not this input's unsealed container; bit 2: the capacity
+// does not hold the trailer — the container is then left as it was.
+hipError_t launch_seal(const uint8_t* d_in, uint64_t input_size, uint8_t* d_container, uint64_t capacity, uint32_t* d_geom, uint32_t* d_acc, uint32_t* d_err,
+                       hipStream_t stream);
+// a trailer of n_chunks words to its place behind the packed container the layout kernel has just written (density_hip_pack_device)
+hipError_t launch_move_trailer(const uint8_t* d_trailer, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err, hipStream_t stream);
+
 }  // namespace density

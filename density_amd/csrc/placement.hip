@@ -1,11 +1,13 @@
 // placement.hip — multi-GPU placement arithmetic of the container path for callers below Python (include/density_hip.h:
-// density_hip_shard_range, density_hip_global_layout).  Host code only: no kernel, no HIP call.  The path shards by chunks (SURVEY.md 8e;
+// density_hip_shard_range, density_hip_global_layout) and the host side of sealed containers (density_hip_checksum32, density_hip_seal_overhead).
+// Host code only: no kernel, no HIP call.  The path shards by chunks (SURVEY.md 8e;
 // there is nothing to match in the reference, whose stream is one chain: codec/codec.rs:72-80); density_amd/parallel.py holds the same
 // arithmetic for torch.distributed callers and tests/test_placement_abi.py holds the two against each other.
 #include <cstdint>
 #include <cstddef>
 
 #include "../../include/density_hip.h"
+#include "checksum.hpp"
 
 namespace {
 inline uint64_t align16(uint64_t v) { return (v + 15u) / 16u * 16u; }
@@ -30,6 +32,8 @@ int density_hip_shard_range(size_t total_len, size_t chunk_size, uint32_t rank, 
 int density_hip_global_layout(const uint64_t* chunks, const uint64_t* payload_bytes, const uint64_t* input_bytes, uint32_t world, uint32_t rank,
                               uint32_t flags, density_hip_global_layout_t* out) {
     if (!chunks || !payload_bytes || !input_bytes || !out || world == 0 || rank >= world) return DENSITY_HIP_ERR_ARGUMENT;
+    // sealed shards are not stitched (their trailers would have to be merged), and a bit that is no container flag is not guessed at
+    if (flags & ~(DENSITY_HIP_FLAG_BLOCK_INDEX | DENSITY_HIP_FLAG_SLOTTED | DENSITY_HIP_FLAG_PAGED)) return DENSITY_HIP_ERR_ARGUMENT;
     // every payload region but the last non-empty one is padded, so that the payload behind it starts 16-byte aligned
     int64_t last = -1;
     for (uint32_t r = 0; r < world; ++r) if (payload_bytes[r] > 0) last = (int64_t)r;
@@ -49,6 +53,30 @@ int density_hip_global_layout(const uint64_t* chunks, const uint64_t* payload_by
     out->payload_at = align16(out->index_at + out->index_bytes);
     out->container_len = out->payload_at + pay_total;                              // (the last region is not padded at its end)
     return DENSITY_HIP_OK;
+}
+
+// ---- sealed containers (include/density_hip.h: DENSITY_HIP_FLAG_CHECKSUM): the checksum as a CPU reader computes it, and what a trailer costs ----
+uint32_t density_hip_checksum32(const uint8_t* data, size_t size) {
+    uint32_t sum = 0;
+    const size_t whole = data ? size / 4 : 0;
+    for (size_t i = 0; i < whole; ++i) {
+        uint32_t w;
+        __builtin_memcpy(&w, data + 4 * i, 4);                                       // (little-endian hosts, like the rest of the container)
+        sum += density::sum_term(w, (uint32_t)i);
+    }
+    if (data && size % 4) {
+        uint32_t w = 0;
+        __builtin_memcpy(&w, data + 4 * whole, size % 4);
+        sum += density::sum_term(w, (uint32_t)whole);
+    }
+    return density::fmix32(sum + (uint32_t)(data ? size : 0));
+}
+
+size_t density_hip_seal_overhead(size_t input_size, size_t chunk_size) {
+    if (chunk_size == 0) chunk_size = 64u << 10;                                     // the smallest automatic chunk of any algorithm: the most chunks
+    if (chunk_size < 256 || chunk_size % 256 != 0 || chunk_size > (1u << 30)) return 0;
+    const uint64_t n_chunks = ((uint64_t)input_size + chunk_size - 1) / chunk_size;
+    return n_chunks > 0xffffffffull ? 0 : (size_t)(16u + align16(4u * n_chunks));
 }
 
 // ---- the multi-rank container "DHCM" (include/density_hip.h): every rank's blob as it stands behind a table of {offset, length, input bytes} ----

@@ -78,7 +78,8 @@ enum {
     DENSITY_HIP_ERR_CAPACITY = 2,     /* output or workspace too small */
     DENSITY_HIP_ERR_FORMAT = 3,       /* container header or payload malformed / truncated */
     DENSITY_HIP_ERR_RUNTIME = 4,      /* HIP runtime error, no gfx950 device, failed self-test */
-    DENSITY_HIP_ERR_UNSUPPORTED = 5   /* the device path does not take these buffers (a paged container or its output not 4-byte aligned) */
+    DENSITY_HIP_ERR_UNSUPPORTED = 5,  /* the device path does not take these buffers (a paged container or its output not 4-byte aligned) */
+    DENSITY_HIP_ERR_CHECKSUM = 6      /* a sealed container decoded without a format error, but not to the bytes that were sealed */
 };
 
 /*
@@ -121,6 +122,20 @@ enum {
  * calls the crate; density_hip_decode_device() reads the pages in place, and only from a container and into an output that are both
  * 4-byte aligned (anything else: DENSITY_HIP_ERR_UNSUPPORTED, nothing written; density_hip_decode() on host pointers stages it aligned). */
 #define DENSITY_HIP_FLAG_PAGED 4u
+/* Sealed container: any of the three forms above, for any algorithm, followed by a trailer of content checksums.  A flipped bit in a PLAIN quad, a
+ * MAP hash or a raw-copy block is a valid stream: the reference decodes it, and so does this library, to total_len wrong bytes.  The trailer catches that.
+ * With E the unsealed container_len: at T = round_up(E, 16) stand n_chunks little-endian u32, entry i = C(input chunk i) (the last chunk at its true
+ * length), zero-padded to a multiple of 16 (the bytes [E, T) are zeros too); container_len becomes T + round_up(4 * n_chunks, 16) and this flag is
+ * set.  A reader finds the trailer from the end: T = container_len - round_up(4 * n_chunks, 16).  Nothing in front of T moves: size table, block index,
+ * directory, pages and payload offsets are those of the unsealed container.  A container of zero chunks seals to itself plus the flag.
+ *     C(B), B of L bytes: m = ceil(L / 4) little-endian 32-bit words w_i, the last zero-padded; all arithmetic mod 2^32:
+ *         S = sum over i of fmix32(w_i + 0x9E3779B1 * (i + 1));   C = fmix32(S + (uint32_t)L);
+ *         fmix32(h): h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16.
+ * A sum, so that any split of a chunk over lanes, work-groups or host slices combines with one add; fmix32 is a bijection and the word's index goes
+ * in, so one damaged word, or two different words exchanged, always change S; random damage passes with probability 2^-32.  It is an INTEGRITY CHECK,
+ * NOT A MAC: anyone who can rewrite the payload can rewrite the trailer.  density_hip_checksum32() below computes C on the host.
+ * density_hip_decode_device() / density_hip_decode() verify a sealed container: they decode as ever, sum their own output on the device and compare. */
+#define DENSITY_HIP_FLAG_CHECKSUM 8u
 #define DENSITY_HIP_PAGE_BYTES 65536u
 #define DENSITY_HIP_MAGIC 0x31434844u /* "DHC1" */
 #define DENSITY_HIP_DEFAULT_CHUNK (1u << 20)
@@ -157,6 +172,11 @@ size_t density_hip_container_bound(int algo, size_t input_size, size_t chunk_siz
 size_t density_hip_encode(int algo, const uint8_t* input, size_t input_size, uint8_t* output, size_t output_size,
                           size_t chunk_size);
 size_t density_hip_decode(const uint8_t* container, size_t container_size, uint8_t* output, size_t output_size);
+/* density_hip_encode() followed by a seal on the device before the copy down (DENSITY_HIP_FLAG_CHECKSUM): the packed form with its trailer.
+ * `output_size` must hold density_hip_container_bound() + density_hip_seal_overhead().  density_hip_decode() verifies a sealed container and returns
+ * 0, with density_hip_last_error() naming the checksum, where the decoded bytes are not the sealed ones.  Sealed containers are staged whole: the
+ * pipelined paths above take unsealed containers only, and the bytes do not depend on the path. */
+size_t density_hip_encode_sealed(int algo, const uint8_t* input, size_t input_size, uint8_t* output, size_t output_size, size_t chunk_size);
 /* Reads total_len from a host-resident container header (0 if malformed). */
 size_t density_hip_decoded_size(const uint8_t* container, size_t container_size);
 
@@ -203,6 +223,25 @@ int density_hip_pack_device(const void* d_container, size_t container_size, cons
 int density_hip_decode_device(const void* d_container, size_t container_size, const density_hip_header_t* header,
                               void* d_output, size_t output_capacity, void* d_workspace, size_t workspace_size,
                               void* stream, size_t* decoded_size_out);
+
+/* Sealed containers on the device (DENSITY_HIP_FLAG_CHECKSUM above).
+ * density_hip_checksum_device: C of every `chunk_size` bytes (a multiple of 256) of a device buffer at any alignment into d_sums[ceil(size / chunk_size)]
+ * (4-byte aligned; cleared by the call).  Asynchronous.
+ * density_hip_seal_device: seals, in place, the container one of the three density_hip_encode_device* calls has just written for d_input; ordered on `stream`
+ * behind that call.  What it needs — chunk size, chunk count, where the container ends — it reads from the header ON THE DEVICE; `header` (optional, HOST) only lets
+ * it refuse at once what it would refuse anyway.  With header_out == NULL there is no host round trip: a one-work-group kernel in front of the sum kernel
+ * checks the header and the capacity, one behind it writes the trailer, the flag and the new container_len, and a container_capacity too small for the
+ * trailer leaves the container unsealed and is not reported (the same contract as the encode calls).  With header_out the call synchronises, returns the
+ * sealed header and reports DENSITY_HIP_ERR_CAPACITY.  DENSITY_HIP_ERR_ARGUMENT: the container is sealed already, or input_size is not its total_len
+ * (seen at once with `header`, on the device otherwise and then reported only with header_out).  Scratch (a word per chunk) comes from the library's
+ * per-device workspace: calls on different streams must not overlap with other calls that use it.
+ * density_hip_decode_device on a sealed container decodes as ever, sums its own output and compares it with the trailer on the device: with
+ * decoded_size_out a mismatch is DENSITY_HIP_ERR_CHECKSUM and *decoded_size_out = 0 (format errors take precedence); without, nothing is reported, like
+ * format errors.  density_hip_pack_device carries the trailer of a sealed slotted container along: byte for byte density_hip_encode_device + density_hip_seal_device
+ * (`output_capacity`: density_hip_container_bound() + density_hip_seal_overhead()). */
+int density_hip_checksum_device(const void* d_data, size_t size, size_t chunk_size, uint32_t* d_sums, void* stream);
+int density_hip_seal_device(const void* d_input, size_t input_size, void* d_container, size_t container_capacity, const density_hip_header_t* header,
+                            void* stream, density_hip_header_t* header_out);
 
 /* Device-resident single reference stream (the format of section 1, device pointers).  `size_out` is a HOST
  * pointer and must be non-NULL: the call synchronises `stream`. */
@@ -272,6 +311,16 @@ typedef struct density_hip_global_layout {
 } density_hip_global_layout_t;
 int density_hip_global_layout(const uint64_t* chunks, const uint64_t* payload_bytes, const uint64_t* input_bytes, uint32_t world, uint32_t rank,
                               uint32_t flags, density_hip_global_layout_t* out);
+/* (Sealed shards are not stitched: a flag word with DENSITY_HIP_FLAG_CHECKSUM, or any bit that is no container flag, is DENSITY_HIP_ERR_ARGUMENT.  Sealed
+ * blobs travel whole in a DHCM super-container, below: a blob's length includes its trailer, and every blob is verified when it is decoded.) */
+
+/* The content checksum C of a sealed container's chunk (DENSITY_HIP_FLAG_CHECKSUM above) on the HOST: pure arithmetic, no device, no HIP call.  What a CPU
+ * reader links: decode chunk i with the crate, then compare density_hip_checksum32(chunk, len) with trailer entry i. */
+uint32_t density_hip_checksum32(const uint8_t* data, size_t size);
+/* Upper bound of what sealing adds to any density_hip_container_bound*(): 16 + round_up(4 * n_chunks, 16); 0 for invalid geometry.  chunk_size 0 = the
+ * automatic chunk; that depends on the algorithm, which this call does not take, so it counts the chunks of the SMALLEST automatic chunk any algorithm
+ * picks (64 KiB): an upper bound for all three. */
+size_t density_hip_seal_overhead(size_t input_size, size_t chunk_size);
 
 /*
  * Config 5's wire form: the MULTI-RANK container "DHCM" (round 6).  Every rank's own container — packed, slotted or PAGED, whatever the rank made: each is a
