@@ -19,10 +19,12 @@ extern "C" {
 }
 
 /// include/density_hip.h section 2, sealed containers (DENSITY_HIP_FLAG_CHECKSUM): what a CPU reader and a host-pointer producer link.  The device-pointer calls
-/// (density_hip_checksum_device, density_hip_seal_device) take a hipStream_t and belong to a caller that already binds HIP; they are declared here in step with the header.
+/// (density_hip_checksum_device, density_hip_seal_device, density_hip_decode_device_verdicts) take a hipStream_t and belong to a caller that already binds HIP; they are declared here in step with the header.
 pub mod sealed {
     pub const DENSITY_HIP_FLAG_CHECKSUM: u16 = 8;
     pub const DENSITY_HIP_ERR_CHECKSUM: i32 = 6;
+    pub const DENSITY_HIP_CHUNK_DAMAGED: u32 = 1;
+    pub const DENSITY_HIP_SALVAGE_BLANK: u32 = 1;
     #[repr(C)]
     pub struct DensityHipHeader { pub magic: u32, pub algo: u8, pub version: u8, pub flags: u16, pub chunk_size: u32, pub n_chunks: u32, pub total_len: u64, pub container_len: u64 }
     #[link(name = "density_hip")]
@@ -34,6 +36,13 @@ pub mod sealed {
         pub fn density_hip_checksum_device(d_data: *const core::ffi::c_void, size: usize, chunk_size: usize, d_sums: *mut u32, stream: *mut core::ffi::c_void) -> i32;
         pub fn density_hip_seal_device(d_input: *const core::ffi::c_void, input_size: usize, d_container: *mut core::ffi::c_void, container_capacity: usize,
                                        header: *const DensityHipHeader, stream: *mut core::ffi::c_void, header_out: *mut DensityHipHeader) -> i32;
+        /// verdicts and salvage: a word per chunk (0 = the chunk's bytes in the output have the trailer's checksum, DENSITY_HIP_CHUNK_DAMAGED otherwise), the output kept;
+        /// flags: DENSITY_HIP_SALVAGE_BLANK zeroes the damaged chunks' bytes.  d_verdicts: device; verdicts and damaged_out: host.
+        pub fn density_hip_decode_device_verdicts(d_container: *const core::ffi::c_void, container_size: usize, header: *const DensityHipHeader, d_output: *mut core::ffi::c_void,
+                                                  output_capacity: usize, d_workspace: *mut core::ffi::c_void, workspace_size: usize, stream: *mut core::ffi::c_void,
+                                                  d_verdicts: *mut u32, flags: core::ffi::c_uint, damaged_out: *mut u32) -> i32;
+        pub fn density_hip_decode_verdicts(container: *const u8, container_size: usize, output: *mut u8, output_size: usize, verdicts: *mut u32,
+                                           verdict_capacity: usize, flags: core::ffi::c_uint, damaged_out: *mut u32) -> usize;
     }
 }
 

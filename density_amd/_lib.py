@@ -14,6 +14,8 @@ ALGO_NAMES = {v: k for k, v in ALGO_IDS.items()}
 DEFAULT_CHUNK = 1 << 20
 
 OK, ERR_ARGUMENT, ERR_CAPACITY, ERR_FORMAT, ERR_RUNTIME, ERR_UNSUPPORTED, ERR_CHECKSUM = range(7)
+CHUNK_DAMAGED = 1       # DENSITY_HIP_CHUNK_DAMAGED: a verdict word
+SALVAGE_BLANK = 1       # DENSITY_HIP_SALVAGE_BLANK: flags of the verdict calls
 
 
 class Header(ctypes.Structure):
@@ -68,6 +70,8 @@ SYMBOLS.update({
     "density_hip_seal_overhead": (_SZ, [_SZ, _SZ]),
     "density_hip_checksum_device": (_I, [_VP, _SZ, _SZ, _VP, _VP]),
     "density_hip_seal_device": (_I, [_VP, _SZ, _VP, _SZ, ctypes.POINTER(Header), _VP, ctypes.POINTER(Header)]),
+    "density_hip_decode_device_verdicts": (_I, [_VP, _SZ, ctypes.POINTER(Header), _VP, _SZ, _VP, _SZ, _VP, _VP, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint32)]),
+    "density_hip_decode_verdicts": (_SZ, [_VP, _SZ, _VP, _SZ, ctypes.POINTER(ctypes.c_uint32), _SZ, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint32)]),
     "density_hip_encode_workspace_size": (_SZ, [_I, _SZ, _SZ]),
     "density_hip_decode_workspace_size": (_SZ, [ctypes.c_uint32]),
     "density_hip_decode_workspace_size_for": (_SZ, [_I, _SZ, _SZ]),

@@ -25,7 +25,12 @@ class DecodeError(Exception):
 
 
 class ChecksumError(DecodeError):
-    """A sealed container (include/density_hip.h: DENSITY_HIP_FLAG_CHECKSUM) decoded without a format error, but not to the bytes that were sealed."""
+    """A sealed container (include/density_hip.h: DENSITY_HIP_FLAG_CHECKSUM) decoded without a format error, but not to the bytes that were sealed.
+    damaged_chunks: the indices of the chunks a verdict decode found damaged, an empty tuple where the call that raised does not know them."""
+
+    def __init__(self, *args, damaged_chunks=()):
+        super().__init__(*args)
+        self.damaged_chunks = tuple(damaged_chunks)
 
 
 def _c_contiguous(ai):

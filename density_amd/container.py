@@ -205,6 +205,37 @@ def decode_device(d_container, container_size, d_out, cap, header=None, stream=0
     return size.value if sync else None
 
 
+def decode_device_verdicts(d_container, container_size, d_out, cap, d_verdicts, header=None, stream=0, workspace=(0, 0), blank=True, sync=True):
+    """decode_device of a SEALED container that keeps its output and says which chunks are damaged: d_verdicts (n_chunks u32 on the device) receives 0 for
+    every chunk whose bytes in d_out have the trailer's checksum, _lib.CHUNK_DAMAGED for the others; with `blank` those chunks' bytes become zeros.
+    Returns (return code, number of damaged chunks) — OK, ERR_CHECKSUM or ERR_FORMAT, each with valid verdicts — or None with sync=False (nothing is
+    reported, the verdicts lie on the device).  Anything else (an unsealed container, a capacity) raises DecodeError."""
+    damaged = ctypes.c_uint32(0)
+    rc = _lib.lib().density_hip_decode_device_verdicts(d_container, container_size, ctypes.byref(header) if header is not None else None, d_out, cap,
+                                                       workspace[0], workspace[1], stream, d_verdicts, _lib.SALVAGE_BLANK if blank else 0,
+                                                       ctypes.byref(damaged) if sync else None)
+    if rc not in (_lib.OK, _lib.ERR_CHECKSUM, _lib.ERR_FORMAT) or (rc == _lib.ERR_FORMAT and "chunks damaged" not in _lib.last_error()):
+        _check(rc, DecodeError)
+    return (rc, damaged.value) if sync else None
+
+
+def decode_verdicts(container, output, blank=True):
+    """decode of a SEALED host-resident container that keeps what survived: returns (bytes written, indices of the damaged chunks); with `blank` the bytes of
+    those chunks are zeros.  Raises ChecksumError (damaged_chunks: all of them) where no chunk is intact, DecodeError for anything that is not damage."""
+    ia, n, k1 = _ro(container)
+    oa, cap, k2 = _rw(output)
+    nc = parse_header(ctypes.string_at(ia, 32)).n_chunks if n >= 32 else 0
+    verdicts = (ctypes.c_uint32 * max(nc, 1))()
+    damaged = ctypes.c_uint32(0)
+    r = _lib.lib().density_hip_decode_verdicts(ia, n, oa, cap, verdicts, nc, _lib.SALVAGE_BLANK if blank else 0, ctypes.byref(damaged))
+    bad = [i for i in range(nc) if verdicts[i]] if damaged.value else []
+    if r == 0 and _lib.last_error():          # 0 with no error == a valid, empty container
+        if nc and damaged.value == nc:
+            raise ChecksumError(_lib.last_error(), damaged_chunks=bad)
+        raise DecodeError(_lib.last_error())
+    return r, bad
+
+
 def stream_encode_device(algo, d_in, n, d_out, cap, stream=0):
     size = ctypes.c_size_t(0)
     _check(_lib.lib().density_hip_stream_encode_device(_lib.ALGO_IDS[algo], d_in, n, d_out, cap, stream, ctypes.byref(size)), EncodeError)

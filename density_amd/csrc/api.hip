@@ -316,6 +316,38 @@ int run_decode_container(DeviceCtx* c, const uint8_t* d_in, size_t container_siz
     return DENSITY_HIP_OK;
 }
 
+// A verdict decode of a sealed container: run_decode_container as it stands (asynchronous: it reports nothing), then the sums it has just left in the
+// workspace held against the trailer once more for a word per chunk and a count, then — with DENSITY_HIP_SALVAGE_BLANK — zeros over the damaged chunks.
+// damaged_out (host, nullable): synchronises; it is written wherever the verdicts are valid, a format error included.
+int run_decode_verdicts(DeviceCtx* c, const uint8_t* d_in, size_t container_size, const density_hip_header_t& h, uint8_t* d_out, size_t cap, uint8_t* ws,
+                        hipStream_t s, size_t ws_size, uint32_t* d_verdicts, unsigned flags, uint32_t* damaged_out) {
+    if (const int rc = run_decode_container(c, d_in, container_size, h, d_out, cap, ws, s, nullptr, ws_size)) return rc;
+    const DecodePlan p = plan_decode(h.algo, h.n_chunks, h.chunk_size);
+    Profiler prof(c, s);
+    hipError_t e = launch_chunk_verdicts(reinterpret_cast<const uint32_t*>(p.produced(ws)), h.total_len, h.chunk_size, h.n_chunks, d_in + (h.container_len - header_trailer(h)),
+                                         d_verdicts, p.damaged(ws), p.err(ws), s);
+    prof.mark("chunk_verdicts");
+    if (flags & DENSITY_HIP_SALVAGE_BLANK) {
+        if (e == hipSuccess) e = launch_blank_chunks(d_out, h.total_len, h.chunk_size, h.n_chunks, d_verdicts, s);
+        prof.mark("blank_chunks");
+    }
+    if (e != hipSuccess) { set_error("kernel launch (verdicts)", e); return DENSITY_HIP_ERR_RUNTIME; }
+    if (damaged_out) {
+        uint32_t h_err = 0, damaged = 0;
+        e = read_back(s, p.err(ws), &h_err, &damaged, p.damaged(ws), sizeof(damaged));
+        if (e != hipSuccess) { set_error("decode (device)", e); return DENSITY_HIP_ERR_RUNTIME; }
+        *damaged_out = damaged;
+        if (h_err) {
+            const bool format = h_err & ~kErrChecksum;
+            char msg[160];
+            std::snprintf(msg, sizeof(msg), "%s: %u of %u chunks damaged", format ? "malformed or truncated container payload" : "checksum mismatch", damaged, h.n_chunks);
+            set_error(msg);
+            return format ? DENSITY_HIP_ERR_FORMAT : DENSITY_HIP_ERR_CHECKSUM;
+        }
+    }
+    return DENSITY_HIP_OK;
+}
+
 // slotted container -> packed container (the wire form): header, size table and block index are copied, the payloads gathered
 int run_pack_container(DeviceCtx* c, const uint8_t* d_in, size_t container_size, const density_hip_header_t& h, uint8_t* d_out, size_t cap, uint8_t* ws,
                        hipStream_t s, density_hip_header_t* header_out) {
@@ -501,6 +533,26 @@ int density_hip_decode_device(const void* d_container, size_t container_size, co
     uint8_t* ws = nullptr;
     if (const int rc = resolve_workspace(c, d_workspace, workspace_size, dp.total, dp.total_with_passes, &ws, &workspace_size)) return rc;
     return run_decode_container(c, (const uint8_t*)d_container, container_size, h, (uint8_t*)d_output, output_capacity, ws, s, decoded_size_out, workspace_size);
+}
+
+int density_hip_decode_device_verdicts(const void* d_container, size_t container_size, const density_hip_header_t* header, void* d_output, size_t output_capacity,
+                                       void* d_workspace, size_t workspace_size, void* stream, uint32_t* d_verdicts, unsigned flags, uint32_t* damaged_out) {
+    g_last_error.clear();
+    if (!d_container || container_size < sizeof(density_hip_header_t) || (!d_output && output_capacity) || (flags & ~DENSITY_HIP_SALVAGE_BLANK) || (uintptr_t)d_verdicts % 4 != 0) {
+        set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT;
+    }
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return DENSITY_HIP_ERR_RUNTIME;
+    std::lock_guard<std::mutex> lk(c->mu);
+    density_hip_header_t h;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (const int rc = container_header(header, d_container, container_size, s, &h)) return rc;
+    if (!(h.flags & DENSITY_HIP_FLAG_CHECKSUM)) { set_error("verdicts: the container is not sealed (no trailer to hold its chunks against)"); return DENSITY_HIP_ERR_ARGUMENT; }
+    if (!d_verdicts && h.n_chunks) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
+    const DecodePlan dp = plan_decode(h.algo, h.n_chunks, h.chunk_size);      // (the workspace rules of density_hip_decode_device)
+    uint8_t* ws = nullptr;
+    if (const int rc = resolve_workspace(c, d_workspace, workspace_size, dp.total, dp.total_with_passes, &ws, &workspace_size)) return rc;
+    return run_decode_verdicts(c, (const uint8_t*)d_container, container_size, h, (uint8_t*)d_output, output_capacity, ws, s, workspace_size, d_verdicts, flags, damaged_out);
 }
 
 int density_hip_checksum_device(const void* d_data, size_t size, size_t chunk_size, uint32_t* d_sums, void* stream) {

@@ -276,4 +276,38 @@ size_t density_hip_decode(const uint8_t* container, size_t container_size, uint8
     return produced;
 }
 
+size_t density_hip_decode_verdicts(const uint8_t* container, size_t container_size, uint8_t* output, size_t output_size, uint32_t* verdicts, size_t verdict_capacity,
+                                   unsigned flags, uint32_t* damaged_out) {
+    g_last_error.clear();
+    if (damaged_out) *damaged_out = 0;
+    if (!container || container_size < sizeof(density_hip_header_t) || (!output && output_size) || (flags & ~DENSITY_HIP_SALVAGE_BLANK)) { set_error("bad argument"); return 0; }
+    density_hip_header_t h;
+    std::memcpy(&h, container, sizeof(h));
+    if (check_header(h, container_size) != DENSITY_HIP_OK) { set_error("bad container header"); return 0; }
+    if (!(h.flags & DENSITY_HIP_FLAG_CHECKSUM)) { set_error("verdicts: the container is not sealed (no trailer to hold its chunks against)"); return 0; }
+    if (h.total_len > output_size) { set_error("output buffer too small"); return 0; }
+    if (h.n_chunks > verdict_capacity || (!verdicts && h.n_chunks)) { set_error("verdict buffer too small"); return 0; }
+    if (h.total_len == 0) return 0;
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    // staged whole, like every sealed container; the verdict words lie behind the output in its staging buffer
+    const size_t verdicts_at = align_up(h.total_len, kAlign);
+    hipError_t e = ensure_staging(c, h.container_len, verdicts_at + 4 * (size_t)h.n_chunks, plan_decode(h.algo, h.n_chunks, h.chunk_size).total_with_passes);
+    if (e == hipSuccess) e = copy_host_side_pinned(c->stage_in.p, container, h.container_len, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) { set_error("staging (H2D)", e); return 0; }
+    uint8_t* d_out = (uint8_t*)c->stage_out.p;
+    uint32_t damaged = h.n_chunks;                                                                   // (written wherever the verdicts are valid)
+    const int rc = run_decode_verdicts(c, (const uint8_t*)c->stage_in.p, h.container_len, h, d_out, h.total_len, (uint8_t*)c->work.p, c->stream, c->work.cap,
+                                       reinterpret_cast<uint32_t*>(d_out + verdicts_at), flags, &damaged);
+    if (rc != DENSITY_HIP_OK && rc != DENSITY_HIP_ERR_CHECKSUM && rc != DENSITY_HIP_ERR_FORMAT) return 0;   // (those three come with verdicts: the driver reports no format error before it has them)
+    const std::string said = g_last_error;
+    e = copy_host_side_pinned(verdicts, d_out + verdicts_at, 4 * (size_t)h.n_chunks, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && damaged < h.n_chunks) e = copy_host_side_pinned(output, d_out, h.total_len, hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) { set_error("staging (D2H)", e); return 0; }
+    g_last_error = said;
+    if (damaged_out) *damaged_out = damaged;
+    return damaged < h.n_chunks ? (size_t)h.total_len : 0;
+}
+
 }  // extern "C"

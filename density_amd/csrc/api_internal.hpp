@@ -306,6 +306,7 @@ EncodePlan plan_encode(int algo, size_t n, size_t chunk);
 struct DecodePlan {
     size_t off_err, off_sizes, off_offsets, off_produced, off_tables, off_zmap, off_pass, total, total_with_passes;
     uint32_t* err(uint8_t* ws) const { return reinterpret_cast<uint32_t*>(ws + off_err); }
+    uint32_t* damaged(uint8_t* ws) const { return err(ws) + 1; }                        // (a verdict decode: the number of damaged chunks)
     uint64_t* sizes(uint8_t* ws) const { return reinterpret_cast<uint64_t*>(ws + off_sizes); }
     uint64_t* offsets(uint8_t* ws) const { return reinterpret_cast<uint64_t*>(ws + off_offsets); }
     uint64_t* produced(uint8_t* ws) const { return reinterpret_cast<uint64_t*>(ws + off_produced); }
@@ -347,6 +348,10 @@ int run_encode_container(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, 
                          uint8_t* ws, hipStream_t s, density_hip_header_t* header_out, Form form = Form::Packed);
 int run_decode_container(DeviceCtx* c, const uint8_t* d_in, size_t container_size, const density_hip_header_t& h, uint8_t* d_out,
                          size_t cap, uint8_t* ws, hipStream_t s, size_t* decoded_out, size_t ws_size = 0);
+// run_decode_container on a SEALED container, then a verdict word per chunk in d_verdicts, the count in p.damaged(ws) and, with DENSITY_HIP_SALVAGE_BLANK in
+// `flags`, zeros over the damaged chunks' output; damaged_out (host, nullable): synchronises and reports
+int run_decode_verdicts(DeviceCtx* c, const uint8_t* d_in, size_t container_size, const density_hip_header_t& h, uint8_t* d_out, size_t cap, uint8_t* ws,
+                        hipStream_t s, size_t ws_size, uint32_t* d_verdicts, unsigned flags, uint32_t* damaged_out);
 // the seal of the container just encoded for d_in (`ws`: plan_seal(n).total bytes); `header`: the caller's copy of its header, or nullptr
 int run_seal_container(DeviceCtx* c, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, const density_hip_header_t* header, uint8_t* ws, hipStream_t s,
                        density_hip_header_t* header_out);

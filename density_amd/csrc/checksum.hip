@@ -6,6 +6,9 @@
 // in flight, mixes each word with its index IN THE CHUNK (not its address: the buffer may start anywhere), and the work-group adds its partial sum
 // to the chunk's accumulator with one global atomic.  The sum commutes, so neither the tiles nor the atomics need an order.  A second, tiny kernel
 // turns the accumulators into C = fmix32(S + L), or compares them with a trailer.
+//
+// Verdicts (density_hip_decode_device_verdicts): the accumulators a verifying decode leaves behind are held against the trailer once more, this time with
+// one word per chunk as the answer, and a fill kernel puts zeros where a damaged chunk's bytes stand.
 #include "checksum.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
@@ -93,6 +96,48 @@ __global__ __launch_bounds__(256) void checksum_finish_kernel(uint32_t* __restri
     else if (sum != ld32u(expect + 4ull * c)) atomicOr(err, kErrChecksum);
 }
 
+// The same comparison with an answer per chunk: verdict[c] = DENSITY_HIP_CHUNK_DAMAGED where chunk c's sum is not the trailer's, 0 where it is; *count
+// (cleared by the launcher) receives the number of damaged chunks.  acc is only read: it holds what checksum_tiles_kernel left for the verifying decode.
+__global__ __launch_bounds__(256) void checksum_verdict_kernel(const uint32_t* __restrict__ acc, uint64_t size, uint32_t chunk, uint32_t n_chunks,
+                                                               const uint8_t* __restrict__ expect, uint32_t* __restrict__ verdict, uint32_t* __restrict__ count,
+                                                               uint32_t* __restrict__ err) {
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= n_chunks) return;
+    const bool damaged = fmix32(acc[c] + chunk_len(size, chunk, c)) != ld32u(expect + 4ull * c);
+    verdict[c] = damaged ? DENSITY_HIP_CHUNK_DAMAGED : 0u;
+    if (damaged) { atomicAdd(count, 1u); atomicOr(err, kErrChecksum); }
+}
+
+// Zeros over the output region of every chunk whose verdict is not 0 (the last chunk at its true length, `out` at any alignment): a chunk is cut into
+// tiles of 16 KiB, a work-group takes tiles in a grid-stride loop and leaves a tile of an intact chunk at its first load — the verdict word.  Inside a
+// tile: bytes up to the first 16-byte boundary of the ADDRESS, 16-byte stores, bytes behind the last whole one.
+constexpr uint32_t kBlankThreads = 256, kBlankStores = 4;
+constexpr uint32_t kBlankTile = kBlankThreads * 16u * kBlankStores;   // 16 KiB per work-group and trip
+constexpr uint32_t kBlankMaxGroups = 256u * 32u;
+__global__ __launch_bounds__(kBlankThreads) void blank_chunks_kernel(uint8_t* __restrict__ out, uint64_t size, uint32_t chunk, uint32_t n_chunks,
+                                                                     const uint32_t* __restrict__ verdict) {
+    const uint32_t tiles = (chunk + kBlankTile - 1) / kBlankTile;
+    const uint64_t units = (uint64_t)n_chunks * tiles;
+    for (uint64_t u = blockIdx.x; u < units; u += gridDim.x) {
+        const uint32_t c = (uint32_t)(u / tiles), t0 = (uint32_t)(u % tiles) * kBlankTile;
+        if (verdict[c] == 0u) continue;
+        const uint32_t len = chunk_len(size, chunk, c);
+        if (t0 >= len) continue;                                             // (the ragged last chunk)
+        const uint32_t n = len - t0 < kBlankTile ? len - t0 : kBlankTile;
+        uint8_t* p = out + (uint64_t)c * chunk + t0;
+        const uint32_t lead = (16u - (uint32_t)((uintptr_t)p & 15u)) & 15u, head = lead < n ? lead : n;
+        const uint32_t full = (n - head) / 16u, tail_at = head + full * 16u; // (full <= 1024: four stores a lane cover it)
+        if (threadIdx.x < head) p[threadIdx.x] = 0;
+        u32x4* q = reinterpret_cast<u32x4*>(p + head);
+#pragma unroll
+        for (uint32_t j = 0; j < kBlankStores; ++j) {
+            const uint32_t i = j * kBlankThreads + threadIdx.x;
+            if (i < full) q[i] = u32x4{0u, 0u, 0u, 0u};
+        }
+        if (threadIdx.x < n - tail_at) p[tail_at + threadIdx.x] = 0;
+    }
+}
+
 // The seal, first step: the header the encoder left on the device says where the trailer goes.  A header that is not this input's (or is sealed
 // already) raises bit 1 of *err, a capacity that does not hold the trailer bit 2; either way d_geom says "no chunks" and nothing more happens.
 // Otherwise the accumulators are cleared for the sum kernel.  One work-group.
@@ -166,6 +211,22 @@ hipError_t launch_checksum(const uint8_t* d_data, uint64_t size, uint32_t chunk,
     if (e == hipSuccess) e = launch_tiles(d_data, size, chunk, n_chunks, nullptr, d_sums, stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(checksum_finish_kernel, dim3((n_chunks + 255u) / 256u), dim3(256), 0, stream, d_sums, size, chunk, n_chunks, d_expect, d_err);
+    return hipGetLastError();
+}
+
+hipError_t launch_chunk_verdicts(const uint32_t* d_acc, uint64_t size, uint32_t chunk, uint32_t n_chunks, const uint8_t* d_expect, uint32_t* d_verdicts,
+                                 uint32_t* d_count, uint32_t* d_err, hipStream_t stream) {
+    const hipError_t e = hipMemsetAsync(d_count, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess || n_chunks == 0) return e;
+    hipLaunchKernelGGL(checksum_verdict_kernel, dim3((n_chunks + 255u) / 256u), dim3(256), 0, stream, d_acc, size, chunk, n_chunks, d_expect, d_verdicts, d_count, d_err);
+    return hipGetLastError();
+}
+
+hipError_t launch_blank_chunks(uint8_t* d_out, uint64_t size, uint32_t chunk, uint32_t n_chunks, const uint32_t* d_verdicts, hipStream_t stream) {
+    if (n_chunks == 0) return hipSuccess;
+    const uint64_t units = (uint64_t)n_chunks * ((chunk + kBlankTile - 1) / kBlankTile);
+    hipLaunchKernelGGL(blank_chunks_kernel, dim3((uint32_t)(units < kBlankMaxGroups ? units : kBlankMaxGroups)), dim3(kBlankThreads), 0, stream, d_out, size, chunk, n_chunks,
+                       d_verdicts);
     return hipGetLastError();
 }
 

@@ -183,6 +183,12 @@ constexpr uint32_t kErrChecksum = 0x100u;   // the bit of a decode's error word 
 // (n_chunks words at any alignment: a trailer) d_sums is scratch and a difference raises kErrChecksum in *d_err instead.
 hipError_t launch_checksum(const uint8_t* d_data, uint64_t size, uint32_t chunk, uint32_t n_chunks, uint32_t* d_sums, const uint8_t* d_expect, uint32_t* d_err,
                            hipStream_t stream);
+// Verdicts: d_acc as launch_checksum with d_expect has just left it (the sums S, nothing else) against the trailer d_expect once more, one word per chunk:
+// d_verdicts[c] = DENSITY_HIP_CHUNK_DAMAGED or 0 (4-byte aligned), *d_count (cleared here) the number of damaged chunks, kErrChecksum into *d_err.
+hipError_t launch_chunk_verdicts(const uint32_t* d_acc, uint64_t size, uint32_t chunk, uint32_t n_chunks, const uint8_t* d_expect, uint32_t* d_verdicts,
+                                 uint32_t* d_count, uint32_t* d_err, hipStream_t stream);
+// zeros over chunk c's bytes of d_out (any alignment; the last chunk at its true length) for every c with d_verdicts[c] != 0
+hipError_t launch_blank_chunks(uint8_t* d_out, uint64_t size, uint32_t chunk, uint32_t n_chunks, const uint32_t* d_verdicts, hipStream_t stream);
 // Seals the container an encoder has just written for d_in, in place, from its header ON THE DEVICE: trailer, flag, new container_len.  d_geom: 4
 // words, d_acc: a word per chunk (at most one per 256 bytes of input) of scratch.  *d_err bit 1: not this input's unsealed container; bit 2: the capacity
 // does not hold the trailer — the container is then left as it was.

@@ -209,14 +209,27 @@ def concat_multi_to_rank0(local_blob, input_bytes_local, algo=0, chunk_size=0, g
     return out
 
 
-def decode_multi_device(blob, out):
-    """Decodes a device-resident super-container rank by rank on THIS device (density_hip_decode_device per row, each blob in place); returns the bytes written."""
+def decode_multi_device(blob, out, salvage=False):
+    """Decodes a device-resident super-container rank by rank on THIS device (density_hip_decode_device per row, each blob in place); returns the bytes written.
+
+    salvage=True (sealed blobs): every row goes through the verdict call with blanking (density_hip_decode_device_verdicts), a damaged blob does not end
+    the walk, and the result is [(rank, damaged chunk indices), ...] for the rows that had any — their damaged chunks are zeros in `out`, everything else
+    is decoded."""
     from . import container
     hdr, rows = parse_multi(blob)
-    at = 0
-    for off, ln, nb in rows:
-        if nb:
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != blob.device or out.numel() < hdr["total_len"]:
+        raise ValueError(f"out must be a contiguous uint8 tensor on {blob.device} of at least {hdr['total_len']} bytes")
+    at, damaged_rows = 0, []
+    for rank, (off, ln, nb) in enumerate(rows):
+        if nb and salvage:
+            h = container.parse_header(bytes(blob[off:off + 32].cpu().numpy()))
+            verdicts = torch.empty(h.n_chunks, dtype=torch.int32, device=blob.device)
+            rc, damaged = container.decode_device_verdicts(blob.data_ptr() + off, ln, out.data_ptr() + at, nb, verdicts.data_ptr(), blank=True)
+            if damaged:
+                damaged_rows.append((rank, torch.nonzero(verdicts).flatten().cpu().tolist()))
+        elif nb:
             got = container.decode_device(blob.data_ptr() + off, ln, out.data_ptr() + at, nb)
-            assert got == nb
+            if got != nb:
+                raise container.DecodeError(f"rank {rank}: decoded {got} bytes where the row says {nb}")
         at += nb
-    return at
+    return damaged_rows if salvage else at

@@ -243,6 +243,34 @@ int density_hip_checksum_device(const void* d_data, size_t size, size_t chunk_si
 int density_hip_seal_device(const void* d_input, size_t input_size, void* d_container, size_t container_capacity, const density_hip_header_t* header,
                             void* stream, density_hip_header_t* header_out);
 
+/* Verdicts and salvage: which chunks of a sealed container are damaged, and the rest of it kept.
+ * density_hip_decode_device_verdicts decodes exactly as density_hip_decode_device does (the same workspace rules, the same three forms, the same kernels) and
+ * then answers per chunk: d_verdicts[i] (n_chunks words on the device, 4-byte aligned) is 0 if and only if the bytes now standing in chunk i's region of
+ * d_output have the checksum the trailer holds for chunk i, DENSITY_HIP_CHUNK_DAMAGED otherwise.  The verdict is about the output's content, so it holds
+ * whatever damaged the chunk: a flipped PLAIN quad that decodes silently, a signature the block index contradicts, a lying size table, a directory entry
+ * the decoder refuses to read through — and a damaged trailer entry, which reports a chunk whose bytes are right.  No pass over the data is added: the sums
+ * the verifying decode has just made are held against the trailer once more by a kernel of a thread per chunk.  With DENSITY_HIP_SALVAGE_BLANK in `flags` the
+ * output region of every damaged chunk (the last chunk at its true length) is then overwritten with zeros: wrong bytes of the right length are what sealing
+ * exists to prevent.  The output is kept in every case.
+ *   - damaged_out == NULL: fully asynchronous, nothing is reported; the verdicts lie on the device for the caller's next kernel on `stream`, and the number
+ *     of damaged chunks in the second 32-bit word of d_workspace where the caller passed one.
+ *   - damaged_out (HOST): the call synchronises `stream`; DENSITY_HIP_OK with *damaged_out == 0 for an intact container, DENSITY_HIP_ERR_CHECKSUM with
+ *     *damaged_out = the number of damaged chunks, DENSITY_HIP_ERR_FORMAT where a decoder raised a format error (it takes precedence, as in
+ *     density_hip_decode_device; *damaged_out and the verdicts are valid then as well and say what survived).
+ *   - an unsealed container has no trailer to hold the chunks against: DENSITY_HIP_ERR_ARGUMENT, nothing written.  So are unknown bits in `flags`.  A header or
+ *     trailer that does not fit container_size is DENSITY_HIP_ERR_FORMAT at once; a container of zero chunks DENSITY_HIP_OK with a count of 0.
+ * density_hip_decode_verdicts is the host-pointer form, staged whole like every sealed container: `verdicts` (HOST, verdict_capacity >= n_chunks words) and
+ * *damaged_out (optional) are filled, and it returns total_len if at least one chunk is intact and no argument or capacity error occurred, else 0;
+ * density_hip_last_error() says how many chunks were damaged ("" for an intact container).
+ * Profiling marks: those of a sealed density_hip_decode_device, then "chunk_verdicts" and, when blanking runs, "blank_chunks". */
+#define DENSITY_HIP_CHUNK_DAMAGED 1u
+#define DENSITY_HIP_SALVAGE_BLANK 1u   /* flags: zero the output region of every damaged chunk */
+int density_hip_decode_device_verdicts(const void* d_container, size_t container_size, const density_hip_header_t* header, void* d_output,
+                                       size_t output_capacity, void* d_workspace, size_t workspace_size, void* stream, uint32_t* d_verdicts,
+                                       unsigned flags, uint32_t* damaged_out);
+size_t density_hip_decode_verdicts(const uint8_t* container, size_t container_size, uint8_t* output, size_t output_size, uint32_t* verdicts,
+                                   size_t verdict_capacity, unsigned flags, uint32_t* damaged_out);
+
 /* Device-resident single reference stream (the format of section 1, device pointers).  `size_out` is a HOST
  * pointer and must be non-NULL: the call synchronises `stream`. */
 int density_hip_stream_encode_device(int algo, const void* d_input, size_t input_size, void* d_output,
