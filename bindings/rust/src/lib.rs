@@ -46,6 +46,19 @@ pub mod sealed {
     }
 }
 
+/// include/density_hip.h section 2, the container forms on the device: a PAGED container (sealed or not) to the packed wire form, byte for byte what
+/// density_hip_encode_device (+ density_hip_seal_device) writes.  Device pointers and a hipStream_t: for a caller that already binds HIP.
+pub mod forms {
+    pub use crate::sealed::DensityHipHeader;
+    pub const DENSITY_HIP_FLAG_PAGED: u16 = 4;
+    #[link(name = "density_hip")]
+    extern "C" {
+        pub fn density_hip_unpage_device(d_container: *const core::ffi::c_void, container_size: usize, header: *const DensityHipHeader, d_output: *mut core::ffi::c_void,
+                                         output_capacity: usize, d_workspace: *mut core::ffi::c_void, workspace_size: usize, stream: *mut core::ffi::c_void,
+                                         header_out: *mut DensityHipHeader) -> i32;
+    }
+}
+
 pub mod errors {
     pub mod encode_error { #[derive(Debug)] pub struct EncodeError {} }
     pub mod decode_error { #[derive(Debug)] pub struct DecodeError {} }

@@ -197,6 +197,76 @@ def pack_device(d_container, container_size, d_out, cap, header=None, stream=0, 
     return hdr
 
 
+def unpage_device(d_container, container_size, d_out, cap, header=None, stream=0, workspace=(0, 0), want_header=True):
+    """Paged container (sealed or not) -> packed container, on the device: byte for byte what encode_device (+ seal_device) writes for the same input.
+    Returns the packed container's header (synchronises) or None."""
+    hdr = _lib.Header() if want_header else None
+    rc = _lib.lib().density_hip_unpage_device(d_container, container_size, ctypes.byref(header) if header is not None else None, d_out, cap,
+                                              workspace[0], workspace[1], stream, ctypes.byref(hdr) if want_header else None)
+    _check(rc, EncodeError)
+    return hdr
+
+
+def unpage(blob):
+    """Paged container (bytes or uint8 array, sealed or not) -> the packed container as a uint8 array, on the HOST: what unpage_device does, stated in
+    numpy.  Header with the PAGED flag dropped, size table and block index as they stand, every chunk's stream — the used bytes of its pages in
+    directory order — at the next 16-byte boundary behind the one before (zeros between), container_len where the last one ends; a sealed container's
+    trailer follows at the next 16-byte boundary.  Raises ValueError for what is not a paged container and for a directory that cannot be followed."""
+    import numpy as np
+    src = np.frombuffer(bytes(blob), dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+    if src.size < 32:
+        raise ValueError("not a container")
+    h = parse_header(src[:32].tobytes())
+    nc = h.n_chunks
+    sealed = bool(h.flags & FLAG_CHECKSUM)
+    if h.magic != 0x31434844 or h.version != 1 or (h.flags & ~FLAG_CHECKSUM) != (FLAG_PAGED | FLAG_BLOCK_INDEX) or h.algo != _lib.ALGO_IDS["chameleon"]:
+        raise ValueError("not a paged container")
+    if h.chunk_size < 256 or h.chunk_size % 256 or nc != (h.total_len + h.chunk_size - 1) // h.chunk_size:
+        raise ValueError("bad container header")
+    ppc = int(_lib.lib().density_hip_paged_pages_per_chunk(h.chunk_size))
+    dir_base = ((32 + 4 * nc + 15) // 16 * 16 + (h.total_len + 255) // 256 + 15) // 16 * 16
+    pages_base = (dir_base + 16 * (ppc + 1) * nc + 255) // 256 * 256
+    trailer = (4 * nc + 15) // 16 * 16 if sealed else 0
+    body = h.container_len - trailer
+    if h.container_len > src.size or body < pages_base or (body - pages_base) % PAGE_BYTES:
+        raise ValueError("bad container header")
+    n_pages = (body - pages_base) // PAGE_BYTES
+    sizes = src[32:32 + 4 * nc].view("<u4").astype(np.int64)
+    directory = src[dir_base:dir_base + 16 * (ppc + 1) * nc].view("<u4").astype(np.int64).reshape(nc, ppc + 1, 4)
+    segments, at = [], dir_base                                  # (source offset, bytes, destination offset) of every page in use
+    for i in range(nc):
+        used = int(directory[i, 0, 0])
+        if not 1 <= used <= ppc:
+            raise ValueError(f"chunk {i}: {used} pages in the directory (1 .. {ppc})")
+        pages, nbytes = directory[i, 1:used + 1, 0], directory[i, 1:used + 1, 2]
+        if (pages >= n_pages).any():
+            raise ValueError(f"chunk {i}: a page beyond the {n_pages} the container holds")
+        if (nbytes > PAGE_BYTES).any():
+            raise ValueError(f"chunk {i}: more than a page of bytes in a page")
+        if int(nbytes.sum()) != int(sizes[i]):
+            raise ValueError(f"chunk {i}: the directory's bytes ({int(nbytes.sum())}) are not the size table's ({int(sizes[i])})")
+        length = min(h.chunk_size, h.total_len - i * h.chunk_size)
+        if int(sizes[i]) > length + length // 256 * 8 + (8 if length % 256 else 0):
+            raise ValueError(f"chunk {i}: a stream longer than the chunk's safe_encode_buffer_size")
+        to = at
+        for page, ln in zip(pages.tolist(), nbytes.tolist()):
+            segments.append((pages_base + page * PAGE_BYTES, ln, to))
+            to += ln
+        end, at = to, (to + 15) // 16 * 16
+    end = end if nc else dir_base
+    total = ((end + 15) // 16 * 16 + trailer) if sealed else end
+    out = np.zeros(total, dtype=np.uint8)
+    out[32:dir_base] = src[32:dir_base]
+    for frm, ln, to in segments:
+        out[to:to + ln] = src[frm:frm + ln]
+    if sealed:
+        out[total - trailer:] = src[body:body + trailer]
+    hdr = _lib.Header.from_buffer_copy(bytes(h))
+    hdr.flags, hdr.container_len = h.flags & ~FLAG_PAGED, total
+    out[:32] = np.frombuffer(bytes(hdr), dtype=np.uint8)
+    return out
+
+
 def decode_device(d_container, container_size, d_out, cap, header=None, stream=0, workspace=(0, 0), sync=True):
     size = ctypes.c_size_t(0)
     rc = _lib.lib().density_hip_decode_device(d_container, container_size, ctypes.byref(header) if header is not None else None, d_out, cap,

@@ -395,6 +395,47 @@ int run_pack_container(DeviceCtx* c, const uint8_t* d_in, size_t container_size,
     return DENSITY_HIP_OK;
 }
 
+// paged container -> packed container: size table and block index are copied, the directory is checked, the pages' used bytes gathered through it
+int run_unpage_container(DeviceCtx* c, const uint8_t* d_in, const density_hip_header_t& h, uint8_t* d_out, size_t cap, uint8_t* ws, hipStream_t s,
+                         density_hip_header_t* header_out) {
+    const DecodePlan p = plan_decode(h.algo, h.n_chunks);
+    uint32_t* d_err = p.err(ws);
+    uint64_t *d_offsets = p.sizes(ws) /* packed offsets */, *d_sizes64 = p.produced(ws);
+    const uint64_t pbase = paged_dir_base(h.n_chunks, h.total_len), pages_base = paged_pages_base(h.n_chunks, h.total_len, h.chunk_size);
+    const uint32_t ppc = paged_pages_per_chunk(h.chunk_size);
+    // a sealed container: the pages end in front of its trailer, which moves behind the packed streams once the layout kernel has said where they end
+    const size_t trailer = header_trailer(h), body_len = h.container_len - trailer;
+    if (cap < container_bound(h.algo, h.total_len, h.chunk_size) + (trailer ? seal_overhead(h.n_chunks) : 0)) {
+        set_error(trailer ? "output capacity below density_hip_container_bound() + density_hip_seal_overhead()" : "output capacity below density_hip_container_bound()");
+        return DENSITY_HIP_ERR_CAPACITY;
+    }
+    Profiler prof(c, s);
+    hipError_t e = hipMemsetAsync(d_err, 0, sizeof(uint32_t), s);
+    // sizes (u64) from the size table where the directory agrees with it, then the packed layout into the output
+    if (e == hipSuccess) e = launch_check_directory(d_in, h.n_chunks, h.chunk_size, h.total_len, pbase, ppc, (uint32_t)((body_len - pages_base) / kPageBytes), d_sizes64, d_err, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_out + sizeof(h), d_in + sizeof(h), pbase - sizeof(h), hipMemcpyDeviceToDevice, s);   // size table + block index
+    density_hip_header_t out_h = h;
+    out_h.flags = h.flags & ~(DENSITY_HIP_FLAG_PAGED | DENSITY_HIP_FLAG_CHECKSUM);
+    out_h.container_len = 0;
+    if (e == hipSuccess) e = launch_layout_encode(d_sizes64, h.n_chunks, out_h, pbase, d_out, cap, d_offsets, d_err, s);
+    prof.mark("layout_encode");
+    if (e == hipSuccess) e = launch_unpage(d_in, h.n_chunks, pbase, pages_base, ppc, d_sizes64, d_offsets, d_out, d_err, s);
+    prof.mark("unpage");
+    if (trailer) {
+        if (e == hipSuccess) e = launch_move_trailer(d_in + body_len, d_out, cap, h.n_chunks, d_err, s);
+        prof.mark("move_trailer");
+    }
+    if (e != hipSuccess) { set_error("kernel launch (unpage)", e); return DENSITY_HIP_ERR_RUNTIME; }
+    if (header_out) {
+        uint32_t h_err = 0;
+        e = read_back(s, d_err, &h_err, header_out, d_out, sizeof(*header_out));
+        if (e != hipSuccess) { set_error("unpage (device)", e); return DENSITY_HIP_ERR_RUNTIME; }
+        if (h_err & 4u) { set_error("a page directory the call cannot follow"); return DENSITY_HIP_ERR_FORMAT; }
+        if (h_err) { set_error("container does not fit the output capacity"); return DENSITY_HIP_ERR_CAPACITY; }
+    }
+    return DENSITY_HIP_OK;
+}
+
 // The seal of the container just written for d_in, in place: every chunk of the INPUT summed (checksum.hip), the trailer behind the container, the flag
 // and the new length in its header.  Where the container ends, and how the input was cut, is read from the header on the device, so that nothing here
 // waits for the encoder; the caller's copy of the header only lets the call refuse at once what the device would refuse.
@@ -515,6 +556,23 @@ int density_hip_pack_device(const void* d_container, size_t container_size, cons
     uint8_t* ws = nullptr;
     if (const int rc = resolve_workspace(c, d_workspace, workspace_size, need, need, &ws)) return rc;
     return run_pack_container(c, (const uint8_t*)d_container, container_size, h, (uint8_t*)d_output, output_capacity, ws, s, header_out);
+}
+
+int density_hip_unpage_device(const void* d_container, size_t container_size, const density_hip_header_t* header, void* d_output,
+                              size_t output_capacity, void* d_workspace, size_t workspace_size, void* stream, density_hip_header_t* header_out) {
+    g_last_error.clear();
+    if (!d_container || container_size < sizeof(density_hip_header_t) || !d_output) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return DENSITY_HIP_ERR_RUNTIME;
+    std::lock_guard<std::mutex> lk(c->mu);
+    density_hip_header_t h;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (const int rc = container_header(header, d_container, container_size, s, &h)) return rc;
+    if (!(h.flags & DENSITY_HIP_FLAG_PAGED)) { set_error("density_hip_unpage_device: not a paged container (density_hip_pack_device takes the packed and slotted forms)"); return DENSITY_HIP_ERR_ARGUMENT; }
+    const size_t need = plan_decode(h.algo, h.n_chunks).total;
+    uint8_t* ws = nullptr;
+    if (const int rc = resolve_workspace(c, d_workspace, workspace_size, need, need, &ws)) return rc;
+    return run_unpage_container(c, (const uint8_t*)d_container, h, (uint8_t*)d_output, output_capacity, ws, s, header_out);
 }
 
 int density_hip_decode_device(const void* d_container, size_t container_size, const density_hip_header_t* header, void* d_output,

@@ -192,6 +192,93 @@ __global__ __launch_bounds__(kCopyThreads) void compact_kernel(const uint8_t* __
     }
 }
 
+// ---- PAGED container -> packed container (density_hip_unpage_device): a check of the page directory, then a gather over it ----
+constexpr uint32_t kPageTiles = kPageBytes / kCopyTile;   // work-groups per page
+static_assert(kPageBytes % kCopyTile == 0, "a page is whole copy tiles");
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 u32x4_u __attribute__((aligned(1)));         // a 16-byte load at any byte phase (gfx950 global memory takes it)
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (uint32_t d = 32; d; d >>= 1) v += bperm(lane ^ d, v);
+    return v;
+}
+__device__ __forceinline__ uint64_t chameleon_safe_size(uint64_t n) { return n + (n / 256) * 8 + ((n % 256) ? 8 : 0); }   // (api_internal.hpp: safe_size)
+
+// A wave per chunk: may the gather follow this chunk's directory?  1 .. pages_per_chunk pages, every page inside the container, at most a page of bytes in
+// each, the bytes adding up to the size table's entry, and that no more than the chunk's worst case (the packed output is sized by it).  sizes[c]: the
+// stream's length for the layout kernel, 0 where the directory is refused — then with bit 4 of *err, and the gather writes nothing at all.  Nothing is
+// read through the directory here, and nothing outside it: `used` is checked before the entries it counts are read.
+__global__ __launch_bounds__(256) void check_directory_kernel(const uint8_t* __restrict__ container, uint32_t n, uint64_t chunk_bytes, uint64_t total_len,
+                                                              uint64_t dir_base, uint32_t pages_per_chunk, uint32_t n_pages, uint64_t* __restrict__ sizes,
+                                                              uint32_t* __restrict__ err) {
+    const uint32_t c = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (c >= n) return;
+    const uint8_t* dir = container + dir_base + 16ull * (pages_per_chunk + 1u) * c;
+    const uint32_t size = ld32u(container + kHeaderBytes + 4ull * c), used = ld32u(dir);
+    bool bad = used == 0 || used > pages_per_chunk;
+    uint32_t sum = 0;                                          // (at most pages_per_chunk pages of 64 KiB: a chunk is at most 1 GiB, its worst case below 2^31)
+    if (!bad)
+        for (uint32_t k = lane; k < used; k += 64u) {
+            const uint8_t* e = dir + 16ull * (k + 1u);
+            const uint32_t page = ld32u(e), bytes = ld32u(e + 8);
+            if (page >= n_pages || bytes > kPageBytes) bad = true;
+            else sum += bytes;
+        }
+    sum = wave_sum(sum);
+    bad = ballot64(bad) != 0;
+    const uint64_t first = (uint64_t)c * chunk_bytes, len = total_len - first < chunk_bytes ? total_len - first : chunk_bytes;
+    if (sum != size || size > chameleon_safe_size(len)) bad = true;
+    if (lane == 0) {
+        sizes[c] = bad ? 0ull : size;
+        if (bad) atomicOr(err, 4u);
+    }
+}
+
+// The gather: one work-group per (chunk, directory slot, 16 KiB tile of the page); slots and tiles not in use leave at once.  A page's used bytes go to the
+// chunk's packed offset plus the bytes of the pages in front of it in the chunk's directory (summed here: a few dozen entries).  The destination has any
+// byte phase: the stores are 16-byte aligned uint4, fed from loads at whatever phase that gives the source; the segment's first and last bytes (less than
+// 16 each) go bytewise, with tile 0.  Every byte of the streams is written once; the zero gap up to the next stream's 16-byte boundary by the work-group
+// that holds the stream's last byte.  The directory was checked (check_directory_kernel): with *err set nothing is read through it.
+__global__ __launch_bounds__(kCopyThreads) void unpage_kernel(const uint8_t* __restrict__ in, uint64_t dir_base, uint64_t pages_base, uint32_t pages_per_chunk,
+                                                              uint32_t n, const uint64_t* __restrict__ sizes, const uint64_t* __restrict__ offsets,
+                                                              uint8_t* __restrict__ out, const uint32_t* __restrict__ err) {
+    if (*err) return;
+    const uint32_t tile = blockIdx.x % kPageTiles, slot = blockIdx.x / kPageTiles % pages_per_chunk, chunk = blockIdx.x / (kPageTiles * pages_per_chunk);
+    const uint8_t* dir = in + dir_base + 16ull * (pages_per_chunk + 1u) * chunk;
+    if (slot >= ld32u(dir)) return;
+    const uint8_t* e = dir + 16ull * (slot + 1u);
+    const uint32_t bytes = ld32u(e + 8);
+    if ((uint64_t)tile * kCopyTile >= bytes) return;           // (an empty page too)
+    __shared__ uint32_t wave_sums[kCopyThreads / 64];
+    uint32_t before = 0;
+    for (uint32_t j = threadIdx.x; j < slot; j += kCopyThreads) before += ld32u(dir + 16ull * (j + 1u) + 8);
+    before = wave_sum(before);
+    if ((threadIdx.x & 63u) == 0) wave_sums[threadIdx.x >> 6] = before;
+    __syncthreads();
+    before = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kCopyThreads / 64; ++w) before += wave_sums[w];
+    const uint8_t* s = in + pages_base + (uint64_t)ld32u(e) * kPageBytes;
+    const uint64_t size = sizes[chunk], end = offsets[chunk] + size;
+    uint8_t* d = out + offsets[chunk] + before;
+    const uint32_t phase = (uint32_t)(0u - (uint32_t)(uintptr_t)d) & 15u, head = phase < bytes ? phase : bytes;
+    const uint32_t full = (bytes - head) / 16u, tail = bytes - head - 16u * full;
+    const uint32_t i0 = tile * (kCopyTile / 16u) + threadIdx.x;
+    u32x4 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const uint32_t i = i0 + (uint32_t)j * kCopyThreads; if (i < full) v[j] = *reinterpret_cast<const u32x4_u*>(s + head + 16ull * i); }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const uint32_t i = i0 + (uint32_t)j * kCopyThreads; if (i < full) *reinterpret_cast<u32x4*>(d + head + 16ull * i) = v[j]; }
+    if (tile != 0) return;
+    if (threadIdx.x < head) d[threadIdx.x] = s[threadIdx.x];
+    const uint32_t t1 = threadIdx.x - 64u, t2 = threadIdx.x - 128u;
+    if (t1 < tail) d[bytes - tail + t1] = s[bytes - tail + t1];
+    // the gap behind the chunk's stream is part of the container: zeros, not whatever the buffer held (none behind the last stream: container_len ends there)
+    if (before + (uint64_t)bytes == size && chunk + 1u < n && t2 < ((0u - (uint32_t)end) & 15u)) out[end + t2] = 0;
+}
+
 // LDS ordering assumptions of chameleon.hip, checked on the device the library is running on.
 __global__ __launch_bounds__(64) void selftest_kernel(uint32_t* __restrict__ fail) {
     __shared__ __attribute__((aligned(16))) uint16_t cells[256];
@@ -276,6 +363,24 @@ hipError_t launch_compact(const uint8_t* d_slots, uint64_t slot_stride, const ui
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(compact_kernel, dim3((uint32_t)blocks), dim3(kCopyThreads), 0, stream, d_slots, slot_stride, d_sizes, d_offsets, tiles,
                        d_container, d_err, more_follow ? 1u : 0u);
+    return hipGetLastError();
+}
+
+hipError_t launch_check_directory(const uint8_t* d_container, uint32_t n_chunks, uint64_t chunk_bytes, uint64_t total_len, uint64_t dir_base,
+                                  uint32_t pages_per_chunk, uint32_t n_pages, uint64_t* d_sizes, uint32_t* d_err, hipStream_t stream) {
+    if (n_chunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(check_directory_kernel, dim3((n_chunks + 3) / 4), dim3(256), 0, stream, d_container, n_chunks, chunk_bytes, total_len, dir_base,
+                       pages_per_chunk, n_pages, d_sizes, d_err);
+    return hipGetLastError();
+}
+
+hipError_t launch_unpage(const uint8_t* d_container, uint32_t n_chunks, uint64_t dir_base, uint64_t pages_base, uint32_t pages_per_chunk,
+                         const uint64_t* d_sizes, const uint64_t* d_offsets, uint8_t* d_out, const uint32_t* d_err, hipStream_t stream) {
+    if (n_chunks == 0) return hipSuccess;
+    const uint64_t blocks = (uint64_t)n_chunks * pages_per_chunk * kPageTiles;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(unpage_kernel, dim3((uint32_t)blocks), dim3(kCopyThreads), 0, stream, d_container, dir_base, pages_base, pages_per_chunk, n_chunks,
+                       d_sizes, d_offsets, d_out, d_err);
     return hipGetLastError();
 }
 

@@ -174,6 +174,14 @@ hipError_t launch_compact(const uint8_t* d_slots, uint64_t slot_stride, const ui
                           uint32_t n_chunks, uint8_t* d_container, const uint32_t* d_err, hipStream_t stream, bool more_follow = false);
 // (`more_follow`: the launch gathers one batch of a container and further streams follow its last one — the alignment gap behind that stream
 // is then zero-filled like the gaps between the launch's own streams, so that a batched gather writes the same bytes as a single one)
+// PAGED container -> packed container (density_hip_unpage_device).  The check: a wave per chunk holds the chunk's directory against the size table and the
+// container (n_pages: the pages it holds); d_sizes[c] = the stream's length, or 0 with bit 4 of *d_err where the gather may not follow the directory.
+hipError_t launch_check_directory(const uint8_t* d_container, uint32_t n_chunks, uint64_t chunk_bytes, uint64_t total_len, uint64_t dir_base,
+                                  uint32_t pages_per_chunk, uint32_t n_pages, uint64_t* d_sizes, uint32_t* d_err, hipStream_t stream);
+// The gather: every page's used bytes to d_out + d_offsets[chunk] + the bytes of the chunk's pages in front of it (any alignment of either buffer), the zero
+// gaps between the streams included; nothing where *d_err is set.
+hipError_t launch_unpage(const uint8_t* d_container, uint32_t n_chunks, uint64_t dir_base, uint64_t pages_base, uint32_t pages_per_chunk,
+                         const uint64_t* d_sizes, const uint64_t* d_offsets, uint8_t* d_out, const uint32_t* d_err, hipStream_t stream);
 // LDS same-address ordering self-test (ascending lane order within one ds instruction). *d_fail != 0 on violation.
 hipError_t launch_selftest(uint32_t* d_fail, hipStream_t stream);
 

@@ -82,14 +82,35 @@ def global_layout(layout, chunk_size, flags):
     return dict(n_chunks=n_chunks, total_len=total_len, index_at=idx_at, index_bytes=n_idx, payload_at=pay_at, container_len=container_len)
 
 
+def _unpaged(local_container):
+    """A PAGED local container brought to the packed form the stitch reads (on its own device: density_hip_unpage_device; a CPU tensor through
+    container.unpage); any other container as it stands."""
+    from . import container
+    if local_container.numel() < HEADER_BYTES:
+        return local_container
+    h = container.parse_header(bytes(local_container[:HEADER_BYTES].cpu().numpy()))
+    if h.magic != MAGIC or not (h.flags & container.FLAG_PAGED):
+        return local_container
+    if local_container.device.type == "cpu":
+        return torch.from_numpy(container.unpage(local_container.contiguous().numpy()))
+    src = local_container.contiguous()
+    cap = container.container_bound("chameleon", h.total_len, h.chunk_size) + container.seal_overhead(h.total_len, h.chunk_size)
+    out = torch.empty(cap, dtype=torch.uint8, device=src.device)
+    with torch.cuda.device(src.device):
+        packed = container.unpage_device(src.data_ptr(), src.numel(), out.data_ptr(), cap, stream=torch.cuda.current_stream().cuda_stream)
+    return out[:packed.container_len]
+
+
 def concat_to_rank0(local_container, chunk_size, group=None):
     """Optional stitch across GPUs: rank 0 receives every rank's size table, block-index slice and payload region and writes
     the global container (valid input for density_hip_decode on one GPU).  Other ranks return None.
 
-    Every shard but the last covers whole chunks (shard_chunks), so block-index slices concatenate without re-basing."""
+    Every shard but the last covers whole chunks (shard_chunks), so block-index slices concatenate without re-basing.  A PAGED local container is
+    brought to the packed form first (its streams are not where the stitch looks for them)."""
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     dev = local_container.device
+    local_container = _unpaged(local_container)
     hdr, table, index, payload = parse_local(local_container)
     lay = exchange_layout(hdr["n_chunks"], payload.numel(), hdr["total_len"], dev, group)
     glob = global_layout(lay, chunk_size, hdr["flags"])

@@ -219,6 +219,23 @@ int density_hip_encode_device_paged(int algo, const void* d_input, size_t input_
  * fit its slots or the container leaves the output unwritten): pass header_out to have it validated. */
 int density_hip_pack_device(const void* d_container, size_t container_size, const density_hip_header_t* header, void* d_output,
                             size_t output_capacity, void* d_workspace, size_t workspace_size, void* stream, density_hip_header_t* header_out);
+/* Paged container -> packed container: the gather density_hip_pack_device does for the slotted form, over the page directory.  The input is a PAGED
+ * container, sealed or not; the output is the packed container of the same chunks with DENSITY_HIP_FLAG_BLOCK_INDEX (and DENSITY_HIP_FLAG_CHECKSUM if the
+ * input was sealed): byte for byte what density_hip_encode_device() (+ density_hip_seal_device()) writes for the same input — header, size table, block
+ * index, the 16-byte-aligned payloads with zero gaps, container_len, the trailer behind round_up(E, 16) — whatever order the pages were taken in.  The page
+ * directory and the unused tails of the pages do not appear.  Both buffers at ANY byte alignment (the pages are not decoded, only moved).
+ *   - `output_capacity`: at least density_hip_container_bound(), plus density_hip_seal_overhead() for a sealed input; less is DENSITY_HIP_ERR_CAPACITY at
+ *     once, nothing written.  Workspace as for decode, or NULL.
+ *   - a container that is not PAGED: DENSITY_HIP_ERR_ARGUMENT, nothing written (density_hip_pack_device is for those).
+ *   - a directory the call cannot follow is DENSITY_HIP_ERR_FORMAT, found on the device by a check that runs in front of the gather, and then no payload
+ *     byte of the output is written for any chunk: a chunk with 0 or more than density_hip_paged_pages_per_chunk() pages, a page number at or beyond the
+ *     pages the container holds, a page's `bytes` above DENSITY_HIP_PAGE_BYTES, the `bytes` of a chunk's pages not adding up to its size-table entry, a
+ *     size-table entry above {algo}_safe_encode_buffer_size of the chunk's input.  The "first input block" field is not interpreted: bytes are moved,
+ *     streams are not parsed.
+ *   - header_out == NULL: fully asynchronous, nothing is reported (a refused directory or a capacity the packed container outgrows leaves the payloads
+ *     unwritten).  With header_out the call synchronises, returns the packed container's header and reports DENSITY_HIP_ERR_FORMAT / _CAPACITY. */
+int density_hip_unpage_device(const void* d_container, size_t container_size, const density_hip_header_t* header, void* d_output,
+                              size_t output_capacity, void* d_workspace, size_t workspace_size, void* stream, density_hip_header_t* header_out);
 /* `header` may be NULL: it is then read back from the device (one small synchronous copy). */
 int density_hip_decode_device(const void* d_container, size_t container_size, const density_hip_header_t* header,
                               void* d_output, size_t output_capacity, void* d_workspace, size_t workspace_size,

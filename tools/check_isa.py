@@ -205,6 +205,15 @@ def main():
         if not meta or any(scratch or spills for _, scratch, _, spills in meta):
             print(f"{name}: scratch / spilled registers: {[(scratch, spills) for _, scratch, _, spills in meta] or 'no metadata found'}")
             bad += 1
+    # container.hip: the paged-to-packed gather moves a page in 16-byte loads (at the source's byte phase) and 16-byte stores, without scratch memory
+    name = next((n for n in funcs if "unpage_kernel" in n), None)
+    meta = list(kernel_meta(notes, "unpage_kernel"))
+    if name is None or not meta or any(scratch or spills for _, scratch, _, spills in meta):
+        print(f"unpage_kernel: not found, or scratch / spilled registers: {[(scratch, spills) for _, scratch, _, spills in meta]}")
+        bad += 1
+    elif sum(t.startswith("global_load_dwordx4") for t in funcs[name]) < 4 or sum(t.startswith("global_store_dwordx4") for t in funcs[name]) < 4:
+        print(f"{name}: the page is not moved in 16-byte loads and stores")
+        bad += 1
     print(f"check_isa: {os.path.basename(lib)}: {total} hand-issued loads in the encoder instances with kept quads, decoder waits checked, {stages} exchange stage kernels without scratch, {rows} Lion row accesses of 16 + 4 bytes, {bad} violation(s)")
     return 1 if bad or not total else 0
 
