@@ -654,9 +654,7 @@ void density_hip_set_kernel_variant(int variant) {
     density::g_stage_audit = on(kVarStageAudit);
     density::g_force_serial_decode = on(kVarSerialDecode);
     density::g_serial_parse = on(kVarSerialParse);
-    density::g_chain_walk = on(kVarChainWalk);
     density::g_lion_one_wave = on(kVarLionOneWave);
-    density::g_walk_blocks = on(kVarWalk64) ? 1 : on(kVarWalk128) ? 4 : 2;
     density::g_rotor_split = density::kRotorSplitDefault != on(kVarRotorOtherSplit);
 }
 

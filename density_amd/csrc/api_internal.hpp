@@ -34,7 +34,7 @@ void set_error(const char* what, hipError_t e = hipSuccess);
 // the bits of density_hip_set_kernel_variant, a test hook: include/density_hip.h says what each one selects (payload bytes are identical in every variant)
 enum Variant : int {
     kVarSimple = 1, kVarNoIndex = 2, kVarRolePipeline = 4, kVarBatchedStitch = 8, kVarLaneCodec = 16, kVarWaveCodec = 32, kVarStageAudit = 64, kVarSerialDecode = 128,
-    kVarPipeAlways = 256, kVarPipeNever = 512, kVarSerialParse = 1024, kVarRotorOtherSplit = 2048, kVarChainWalk = 4096, kVarWalk64 = 8192, kVarWalk128 = 16384,
+    kVarPipeAlways = 256, kVarPipeNever = 512, kVarSerialParse = 1024, kVarRotorOtherSplit = 2048,   // (4096, 8192, 16384: reserved)
     kVarLionOneWave = 32768,
     kVarNoRotor = kVarSimple | kVarRolePipeline,   // either way the wave-rotation kernels, and with them segments and pages, are out
 };

@@ -1,5 +1,5 @@
 // decode_passes.hip — Cheetah container DECODING in passes (gfx950): everything that is parallel inside a chunk runs as ordered LDS
-// exchange passes over the whole chunk, and what is not — one chain of dependent 16-bit look-ups per chunk — runs alone, in LDS.
+// exchange passes over the whole chunk, and what is not — one chain of dependent 16-bit look-ups per chunk (decode_walk.hip) — runs alone, in LDS.
 //
 // The reference decodes a chunk quad by quad through three tables (cheetah.rs:68-103,154-163).  Taken apart:
 //
@@ -40,8 +40,6 @@ namespace density {
 extern __shared__ __attribute__((aligned(16))) uint8_t pass_lds[];
 bool g_force_serial_decode = false;   // density_hip_set_kernel_variant(128): Cheetah containers on the one-wave decoder instead
 bool g_serial_parse = false;          // density_hip_set_kernel_variant(1024): the records of a chunk found by the one-wave walk alone (no window kernels)
-bool g_chain_walk = false;            // density_hip_set_kernel_variant(4096): the contexts walked run by run (round 5's walk) instead of 64 quads at a time
-int g_walk_blocks = 2;                // 2: the walk by a team of four waves (default); 1 / 4: by ONE wave, 64 / 128 quads at a time (density_hip_set_kernel_variant bits 13-14: cross-checks)
 
 namespace {
 
@@ -690,725 +688,14 @@ __global__ __launch_bounds__(kPassWaves * 64) void cheetah_pass(PassArgs a) {
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// walk: the contexts (cheetah.rs:97-102,161: last_hash) — the one chain of the decoder, on 16-bit hashes in LDS
-// ---------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kWalkTable = 65536u * 2u, kTileBlocks = 16, kTileBytes = kTileBlocks * 256u, kWalkLds = kWalkTable + 2u * kTileBytes;
-// VEC (round 6): 64 quads at a time.  The chain is only as long as its DEPENDENT links: a predicted quad's context is the hash of the quad before it,
-// which is in the descriptor unless that quad was predicted too — in 100 MB of prose four of five predicted quads follow a quad that was not.  So per
-// block of 64 quads (a quad per lane):
-//   speculate  the contexts of the lanes behind predicted quads by plain READS of H as it stands, level by level (a lane's level = the predicted lanes
-//              right in front of it: one LDS round trip per level for all 64 lanes, where the run-by-run walk paid one per run and quad);
-//   execute    ALL 64 table operations in one ordered instruction (ds_mskor_rtn_b32 on the 16-bit halves: gfx950 serves the lanes of one LDS
-//              instruction in ascending order — §4.2 of DESIGN.md, verified at start-up —, a predicted lane reads, the others write H[context]);
-//   verify     a predicted lane must have read in the ordered pass what its successors' contexts were derived from.  If every one did, the contexts
-//              ARE the sequential ones (induction over the lanes: lane 0's context is the running one; if lanes 0..i hold the right contexts the
-//              ordered pass did to H exactly what cheetah.rs:72,81,90,97-102 do up to quad i, so what lane i read is right, and with it lane i+1's
-//              context).  If lane i0 is the first that read something else (a context written earlier in the SAME block: "the " twice within 256
-//              bytes with two followers), lanes 0..i0 stand, the lanes behind it take their writes back — old halves, highest lane first: the lane-
-//              reversed store of rotor.hip — and go again from what lane i0 really read.
-// Blocks with a run of eight and more predicted quads (periodic input, zeros) keep the run-by-run chain below: a level costs what a link does.
-// NB > 1: NB blocks (128 / 256 quads, NB registers per lane) go through speculate / execute / verify TOGETHER — the levels' reads of all of them are in
-// flight at once, the ordered pass is NB instructions back to back (a wave's LDS instructions execute in issue order: block 0's lanes, then block 1's ...),
-// so the LDS round trips, which are what a lone wave waits for, are shared by NB blocks; a wrong speculation costs one more pass over what lies behind it.
-// lane-mask select: mask[lane] ? a : b with the mask in a scalar register pair (one VALU instruction; the compiler's own form of "(m >> lane) & 1" is three)
-__device__ __forceinline__ uint32_t msel(uint64_t m, uint32_t ifset, uint32_t ifclear) {
-    uint32_t r;
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(ifclear), "v"(ifset), "s"(m));
-    return r;
-}
-// G LDS operations issued back to back and waited for inside ONE statement (an answer in flight lives in a register the compiler believes written:
-// nothing but the wait may stand between issue and use)
-template <uint32_t G>
-__device__ __forceinline__ void lds_read_u16_group(uint32_t (&r)[G], const uint32_t (&addr)[G]) {
-    static_assert(G == 1 || G == 2 || G == 4, "group of 1, 2 or 4 blocks");
-    if constexpr (G == 1) asm volatile("ds_read_u16 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(r[0]) : "v"(addr[0]) : "memory");
-    else if constexpr (G == 2) asm volatile("ds_read_u16 %0, %2\n\tds_read_u16 %1, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(r[0]), "=&v"(r[1]) : "v"(addr[0]), "v"(addr[1]) : "memory");
-    else asm volatile("ds_read_u16 %0, %4\n\tds_read_u16 %1, %5\n\tds_read_u16 %2, %6\n\tds_read_u16 %3, %7\n\ts_waitcnt lgkmcnt(0)"
-                      : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]) : "v"(addr[0]), "v"(addr[1]), "v"(addr[2]), "v"(addr[3]) : "memory");
-}
-template <uint32_t G>
-__device__ __forceinline__ void lds_mskor_group(uint32_t (&r)[G], const uint32_t (&addr)[G], const uint32_t (&mk)[G], const uint32_t (&vl)[G]) {
-    if constexpr (G == 1) asm volatile("ds_mskor_rtn_b32 %0, %1, %2, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(r[0]) : "v"(addr[0]), "v"(mk[0]), "v"(vl[0]) : "memory");
-    else if constexpr (G == 2) asm volatile("ds_mskor_rtn_b32 %0, %2, %4, %6\n\tds_mskor_rtn_b32 %1, %3, %5, %7\n\ts_waitcnt lgkmcnt(0)"
-                                            : "=&v"(r[0]), "=&v"(r[1]) : "v"(addr[0]), "v"(addr[1]), "v"(mk[0]), "v"(mk[1]), "v"(vl[0]), "v"(vl[1]) : "memory");
-    else asm volatile("ds_mskor_rtn_b32 %0, %4, %8, %12\n\tds_mskor_rtn_b32 %1, %5, %9, %13\n\tds_mskor_rtn_b32 %2, %6, %10, %14\n\tds_mskor_rtn_b32 %3, %7, %11, %15\n\ts_waitcnt lgkmcnt(0)"
-                      : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3])
-                      : "v"(addr[0]), "v"(addr[1]), "v"(addr[2]), "v"(addr[3]), "v"(mk[0]), "v"(mk[1]), "v"(mk[2]), "v"(mk[3]), "v"(vl[0]), "v"(vl[1]), "v"(vl[2]), "v"(vl[3]) : "memory");
-}
-// One block of 64 quads that all take part, some of them predicted: the chain run by run, in as few instructions as it takes (the comments are at its
-// use in cheetah_walk).  c: the running context in, out; returns every lane's context.
-__device__ __forceinline__ uint32_t walk_chain_block(uint32_t lds0, uint32_t& c, uint32_t hprev, uint32_t h, uint32_t hw, uint64_t Pin) {
-    const uint64_t P = ((uint64_t)rfl((uint32_t)(Pin >> 32)) << 32) | rfl((uint32_t)Pin);   // (wave-uniform by construction: said so to the register allocator)
-    uint32_t av = lds0 + 2u * hprev;
-    const uint32_t h2 = lds0 + 2u * h;                                      // what the running context becomes behind a quad that is not predicted
-    uint64_t prem = P;
-    uint32_t c2 = rfl(lds0 + 2u * c);
-    uint32_t s_pos, s_p, s_r, v_t, v_u, s_m0;
-    uint64_t s_m;
-    asm volatile(
-        "s_mov_b32 %[m0s], m0\n\t"                                            // (M0 is the compiler's: handed back as found)
-        "s_mov_b32 %[pos], 0\n"
-        "1:\n\t"                                                             // ---- next run of quads that are not predicted: [pos, p)
-        "s_ff1_i32_b64 %[p], %[prem]\n\t"
-        "s_min_u32 %[p], %[p], 64\n\t"                                       // (no predicted quad left: -1 -> 64)
-        "s_sub_u32 %[r], %[p], %[pos]\n\t"
-        "s_cmp_eq_u32 %[r], 0\n\t"
-        "s_cbranch_scc1 2f\n\t"
-        "s_bfm_b64 %[m], %[r], %[pos]\n\t"                                   // r bits from pos on (r < 64: some quad is predicted)
-        "s_mov_b32 m0, %[pos]\n\t"
-        "s_add_u32 %[r], %[p], -1\n\t"
-        "v_writelane_b32 %[av], %[c2], m0\n\t"
-        "s_mov_b64 exec, %[m]\n\t"
-        "ds_write_b16 %[av], %[h]\n\t"
-        "s_mov_b64 exec, -1\n\t"
-        "v_readlane_b32 %[c2], %[h2], %[r]\n"
-        "2:\n\t"
-        "s_cmp_ge_u32 %[p], 64\n\t"
-        "s_cbranch_scc1 4f\n\t"
-        "v_mov_b32 %[t], %[c2]\n"
-        // ---- a predicted quad at lane p: c <- H[c] (cheetah.rs:97-102).  Round 4: the chain is the read, one add and the branch — ~85 cycles
-        // instead of ~105.  The address of H[c] (`t`, the same in every lane) goes into lane p's `av` by a select under a one-lane mask, the
-        // bookkeeping and the test "is the next quad predicted too" are issued while the read is in flight (its answer lands in `u`, so `t`
-        // stays readable), and the scalar copy of the context is taken once per run instead of once per quad.
-        "3:\n\t"
-        "ds_read_u16 %[u], %[t]\n\t"
-        "s_bfm_b64 %[m], 1, %[p]\n\t"
-        "s_bitset0_b64 %[prem], %[p]\n\t"
-        "s_add_u32 %[p], %[p], 1\n\t"
-        "v_cndmask_b32_e64 %[av], %[av], %[t], %[m]\n\t"
-        "s_bitcmp1_b64 %[prem], %[p]\n\t"                                    // (p == 64 tests bit 0, which is clear by now: lane 0 was either not predicted or has been taken)
-        "s_waitcnt lgkmcnt(0)\n\t"
-        "v_lshl_add_u32 %[t], %[u], 1, %[lds0]\n\t"
-        "s_cbranch_scc1 3b\n\t"
-        "s_nop 0\n\t"
-        "v_readfirstlane_b32 %[c2], %[t]\n\t"
-        "s_cmp_ge_u32 %[p], 64\n\t"
-        "s_cbranch_scc1 4f\n\t"
-        "s_mov_b32 %[pos], %[p]\n\t"
-        "s_branch 1b\n"
-        "4:\n\t"
-        "s_mov_b32 m0, %[m0s]\n\t"
-        : [av] "+v"(av), [c2] "+s"(c2), [prem] "+s"(prem), [pos] "=&s"(s_pos), [p] "=&s"(s_p), [r] "=&s"(s_r), [m] "=&s"(s_m), [t] "=&v"(v_t), [u] "=&v"(v_u), [m0s] "=&s"(s_m0)
-        : [h] "v"(hw), [h2] "v"(h2), [lds0] "s"(lds0)
-        : "memory", "scc");
-    c = (c2 - lds0) >> 1;
-    return (av - lds0) >> 1;
-}
-
-template <int NB>
-__global__ __launch_bounds__(64) void cheetah_walk(PassArgs a) {
-    constexpr bool VEC = NB >= 1;
-    constexpr uint32_t G = NB > 1 ? NB : 1;
-    const uint32_t lane = threadIdx.x;
-    const uint64_t chunk = blockIdx.x;
-    const ChunkInfo ci = a.info[chunk];
-    if (ci.bad) return;
-    const uint32_t nsteps = ci.blocks * kRecQuads;
-    const uint32_t nblk = (nsteps + 63u) / 64u;
-    const uint64_t s0 = chunk * (a.out_stride / 4);
-    const uint32_t* __restrict__ desc = a.desc + s0;
-    uint16_t* __restrict__ ctx = a.ctx + s0;
-    const uint32_t* __restrict__ val = reinterpret_cast<const uint32_t*>(a.out + chunk * a.out_stride);
-    {   // H starts as the hash of the reference's zeroed prediction table: hash(0) = 0
-        uint4* p = reinterpret_cast<uint4*>(pass_lds);
-        for (uint32_t i = lane; i < kWalkTable / 16; i += 64) p[i] = make_uint4(0, 0, 0, 0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-    const uint32_t lds0 = lds_addr(pass_lds);
-    uint32_t* stage = reinterpret_cast<uint32_t*>(pass_lds + kWalkTable);           // two tiles of 16 blocks of descriptors
-    uint32_t c = 0;                                                                // cheetah.rs:52: last_hash = 0
-    // The chain below never waits for memory: the descriptors of tile t + 1 are in flight (registers) while tile t is walked out of LDS
-    // (one wave has one load's latency — microseconds — per request: with a block per request the walk ran at the speed of its loads).
-    uint32_t tile[kTileBlocks];
-    auto fetch = [&](uint32_t t) {
-#pragma unroll
-        for (uint32_t j = 0; j < kTileBlocks; ++j) {
-            const uint32_t i = (t * kTileBlocks + j) * 64u + lane;
-            tile[j] = i < nsteps ? desc[i] : kDescNone;
-        }
-    };
-    auto land = [&](uint32_t t) {
-#pragma unroll
-        for (uint32_t j = 0; j < kTileBlocks; ++j) stage[(t & 1u) * (kTileBytes / 4) + j * 64u + lane] = tile[j];
-    };
-    fetch(0); land(0);
-    // a MAP quad's hash — the next quad's context — is its item, a PLAIN quad's the hash of its value (in the descriptor either way); a predicted
-    // quad's comes out of H, which holds per context the hash of the VALUE last left there (`hw`)
-    for (uint32_t blk = 0; blk < nblk; ++blk) {
-        const uint32_t t = blk / kTileBlocks, j = blk % kTileBlocks;
-        if (j == 0) fetch(t + 1u);
-        if (NB > 1 && j % G == 0 && blk + G <= nblk) {
-            // ---- a group of G blocks, if every one of them is whole and has no long run ----
-            uint32_t dv[G], hv[G], hwv[G], cvv[G], rsv[G], rfv[G], r2v[G], shv[G];
-            uint64_t Pm[G], Nm[G], K0m[G], known[G], fin[G], rdone[G];
-            bool ok = true;
-#pragma unroll
-            for (uint32_t b = 0; b < G; ++b) {
-                dv[b] = stage[(t & 1u) * (kTileBytes / 4) + (j + b) * 64u + lane];
-                hv[b] = dv[b] & 0xffffu;
-                hwv[b] = (dv[b] & kDescZero) ? 0u : hv[b];
-                const bool none = (dv[b] & kDescNone) != 0, pred = ((dv[b] >> 16) & 3u) == kFlagPred;
-                Pm[b] = ballot64(!none && pred); Nm[b] = ballot64(!none && !pred);
-                uint64_t lr = Pm[b] & (Pm[b] >> 1); lr &= lr >> 2; lr &= lr >> 4;
-                ok = ok && (Pm[b] | Nm[b]) == ~0ull && lr == 0;
-            }
-            if (__builtin_expect(ok, 1)) {
-                if (j + G == kTileBlocks || blk + G == nblk) land(t + 1u);
-#pragma unroll
-                for (uint32_t b = 0; b < G; ++b) {
-                    const uint32_t hp = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hv[b], 0x138, 0xf, 0xf, false);   // wave_shr:1
-                    const uint32_t first = b == 0 ? c : (uint32_t)__builtin_amdgcn_readlane((int)hv[b ? b - 1 : 0], 63);   // (meaningful only where the quad before was not predicted)
-                    cvv[b] = lane == 0 ? first : hp;
-                    K0m[b] = (Nm[b] << 1) | (b == 0 ? 1ull : (Nm[b ? b - 1 : 0] >> 63));
-                    known[b] = K0m[b]; fin[b] = 0; rsv[b] = 0; rfv[b] = 0;
-                }
-                for (;;) {
-                    // speculate: every level's reads of all G blocks in flight together
-#pragma unroll
-                    for (uint32_t b = 0; b < G; ++b) rdone[b] = fin[b];
-                    for (;;) {
-                        uint64_t R[G], any = 0;
-#pragma unroll
-                        for (uint32_t b = 0; b < G; ++b) { R[b] = Pm[b] & known[b] & ~rdone[b]; any |= R[b]; }
-                        if (!any) break;
-                        uint32_t r[G], ad[G];
-#pragma unroll
-                        for (uint32_t b = 0; b < G; ++b) ad[b] = lds0 + 2u * cvv[b];
-                        lds_read_u16_group<G>(r, ad);                                  // (every block reads, whether or not one of its lanes needs it: a stale context is a valid address)
-#pragma unroll
-                        for (uint32_t b = 0; b < G; ++b) {
-                            const uint64_t in = (R[b] << 1) | (b == 0 ? 0ull : (R[b ? b - 1 : 0] >> 63));   // the lanes that learn their context this round
-                            if (R[b]) rsv[b] = msel(R[b], r[b], rsv[b]);
-                            if (in) {
-                                uint32_t up = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r[b], 0x138, 0xf, 0xf, false);   // wave_shr:1
-                                if (b != 0 && (in & 1ull)) { const uint32_t carry = (uint32_t)__builtin_amdgcn_readlane((int)r[b ? b - 1 : 0], 63); up = lane == 0 ? carry : up; }
-                                cvv[b] = msel(in, up, cvv[b]);
-                            }
-                            known[b] |= in; rdone[b] |= R[b];
-                        }
-                    }
-                    // execute: the lanes that do not stand yet, block after block, each in lane order
-                    uint32_t ret[G], xa[G], xm[G], xv[G];
-#pragma unroll
-                    for (uint32_t b = 0; b < G; ++b) {
-                        shv[b] = (cvv[b] & 1u) * 16u;
-                        const uint64_t w = Nm[b] & ~fin[b];
-                        xa[b] = lds0 + ((2u * cvv[b]) & ~3u);
-                        xm[b] = msel(w, 0xffffu << shv[b], 0u); xv[b] = msel(w, hwv[b] << shv[b], 0u);
-                    }
-                    lds_mskor_group<G>(ret, xa, xm, xv);
-                    // verify
-                    uint64_t bad[G], anybad = 0;
-#pragma unroll
-                    for (uint32_t b = 0; b < G; ++b) {
-                        r2v[b] = (ret[b] >> shv[b]) & 0xffffu;
-                        bad[b] = ballot64(r2v[b] != rsv[b]) & Pm[b] & ~fin[b];
-                        anybad |= bad[b];
-                    }
-                    if (__builtin_expect(anybad == 0, 1)) {
-#pragma unroll
-                        for (uint32_t b = 0; b < G; ++b) rfv[b] = msel(~fin[b], r2v[b], rfv[b]);
-                        break;
-                    }
-                    uint32_t b0 = 0;
-#pragma unroll
-                    for (uint32_t b = G; b-- > 0;) if (bad[b]) b0 = b;
-                    uint64_t badb = bad[0];
-#pragma unroll
-                    for (uint32_t b = 1; b < G; ++b) badb = b0 == b ? bad[b] : badb;
-                    const uint32_t i0 = (uint32_t)__builtin_ctzll(badb);
-                    const uint64_t upto = (2ull << i0) - 1ull;                           // lanes 0 .. i0 of block b0 (i0 == 63: all of them)
-                    uint64_t stands[G];
-#pragma unroll
-                    for (uint32_t b = 0; b < G; ++b) stands[b] = b < b0 ? ~0ull : b == b0 ? upto : 0ull;
-                    // the writes behind the first wrong read are taken back: old halves, the latest write first (blocks from the last to b0, lanes reversed)
-#pragma unroll
-                    for (uint32_t b = G; b-- > 0;) {
-                        const uint64_t undo = Nm[b] & ~stands[b] & ~fin[b];
-                        if (undo) {
-                            const uint32_t ar = bperm(63u - lane, lds0 + 2u * cvv[b]), old = bperm(63u - lane, r2v[b]);
-                            if ((undo >> (63u - lane)) & 1ull) asm volatile("ds_write_b16 %0, %1" ::"v"(ar), "v"(old) : "memory");
-                        }
-                    }
-                    const uint32_t truth = (uint32_t)__builtin_amdgcn_readlane((int)(b0 == 0 ? r2v[0] : b0 == 1 ? r2v[G > 1 ? 1 : 0] : b0 == 2 ? r2v[G > 2 ? 2 : 0] : r2v[G > 3 ? 3 : 0]), (int)i0);
-                    bool all = true;
-#pragma unroll
-                    for (uint32_t b = 0; b < G; ++b) {
-                        rfv[b] = msel(stands[b] & ~fin[b], r2v[b], rfv[b]);
-                        fin[b] = stands[b];
-                        all = all && fin[b] == ~0ull;
-                        // the lane behind (b0, i0) now knows its context; everything else behind it is as unknown as before the first round
-                        const uint64_t next = b == b0 ? (i0 == 63u ? 0ull : (2ull << i0) & ~upto) : (b == b0 + 1u && i0 == 63u ? 1ull : 0ull);
-                        if (next) cvv[b] = msel(next, truth, cvv[b]);
-                        known[b] = stands[b] | next | K0m[b];
-                    }
-                    if (all) break;
-                }
-                const uint32_t last = msel(Pm[G - 1], rfv[G - 1], hv[G - 1]);
-                c = (uint32_t)__builtin_amdgcn_readlane((int)last, 63);
-#pragma unroll
-                for (uint32_t b = 0; b < G; ++b) { const uint32_t i = (blk + b) * 64u + lane; if (i < nsteps) ctx[i] = (uint16_t)cvv[b]; }
-                blk += G - 1u;
-                continue;
-            }
-        }
-        const uint32_t d = stage[(t & 1u) * (kTileBytes / 4) + j * 64u + lane];
-        if (j == kTileBlocks - 1u || blk + 1u == nblk) land(t + 1u);                 // (behind the read of the tile's last block: the other buffer)
-        const uint32_t h = d & 0xffffu;
-        const uint32_t hw = (d & kDescZero) ? 0u : h;                              // what H takes for this quad: the hash of its VALUE (kDescZero: a MAP quad that read a never-written 0)
-        const bool none = (d & kDescNone) != 0, pred = ((d >> 16) & 3u) == kFlagPred;
-        const uint64_t P = ballot64(!none && pred), N = ballot64(!none && !pred);
-        // what the quad before me hashed to: my context if that quad was not predicted (lane 0: the running context)
-        const uint32_t hprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)h, 0x138, 0xf, 0xf, false);   // wave_shr:1
-        uint32_t cv = hprev;                                                       // my context: the hash of the quad before me, unless patched below
-        const uint64_t active = P | N;
-        uint64_t longrun = P & (P >> 1); longrun &= longrun >> 2; longrun &= longrun >> 4;   // bit i: lanes i .. i+7 are all predicted
-        if (VEC && __builtin_expect(active == ~0ull && longrun == 0, 1)) {
-            const uint64_t K0 = (N << 1) | 1ull;                                     // lanes whose context is in the descriptors (lane 0: the running context)
-            cv = lane == 0 ? c : hprev;
-            const bool lp = (P >> lane) & 1ull;
-            uint64_t fin = 0, known = K0;
-            uint32_t rfin = 0;                                                       // predicted lanes: what they read (their successor's context)
-            for (;;) {
-                // speculate
-                uint32_t rs = 0;
-                uint64_t rdone = fin;
-                for (;;) {
-                    const uint64_t R = P & known & ~rdone;
-                    if (!R) break;
-                    uint32_t r;
-                    asm volatile("ds_read_u16 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(lds0 + 2u * cv) : "memory");
-                    const uint32_t up = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x138, 0xf, 0xf, false);   // wave_shr:1
-                    if ((R >> lane) & 1ull) rs = r;
-                    if (((R << 1) >> lane) & 1ull) cv = up;
-                    known |= R << 1; rdone |= R;
-                }
-                // execute: every lane that does not stand yet, in stream order
-                const bool pend = !((fin >> lane) & 1ull), wr = pend && !lp;
-                const uint32_t sh = (cv & 1u) * 16u;
-                uint32_t ret;
-                asm volatile("ds_mskor_rtn_b32 %0, %1, %2, %3\n\ts_waitcnt lgkmcnt(0)" : "=v"(ret) : "v"(lds0 + ((2u * cv) & ~3u)), "v"(wr ? 0xffffu << sh : 0u), "v"(wr ? hw << sh : 0u) : "memory");
-                const uint32_t r2 = (ret >> sh) & 0xffffu;
-                // verify
-                const uint64_t bad = ballot64(pend && lp && r2 != rs);
-                if (__builtin_expect(bad == 0, 1)) { if (pend) rfin = r2; break; }
-                const uint32_t i0 = (uint32_t)__builtin_ctzll(bad);
-                const uint64_t stands = (2ull << i0) - 1ull;                           // lanes 0 .. i0 (i0 == 63: all of them)
-                const uint64_t undo = N & ~stands;                                   // the writes behind i0 (every pending lane beyond i0 that is not predicted wrote)
-                if (undo) {
-                    const uint32_t ar = bperm(63u - lane, lds0 + 2u * cv), old = bperm(63u - lane, r2);
-                    if ((undo >> (63u - lane)) & 1ull) asm volatile("ds_write_b16 %0, %1" ::"v"(ar), "v"(old) : "memory");
-                }
-                if (pend && ((stands >> lane) & 1ull)) rfin = r2;
-                fin = stands;
-                if (fin == ~0ull) break;
-                const uint32_t truth = (uint32_t)__builtin_amdgcn_readlane((int)r2, (int)i0);
-                if (lane == i0 + 1u) cv = truth;
-                known = stands | (stands << 1) | K0;
-            }
-            const uint32_t last = lp ? rfin : h;
-            c = (uint32_t)__builtin_amdgcn_readlane((int)last, 63);
-        } else
-        if (__builtin_expect(active == ~0ull && P != 0 && P != ~0ull, 1)) {
-            // Every quad of the block takes part (no raw-copy block, not the chunk's end) and some, not all, are predicted: the chain in as
-            // few instructions as it takes — a lone wave issues one instruction every 4-5 cycles, so the instruction count IS the walk's
-            // time (the compiled form of the loop below spent ~110 instructions per run, this one ~29).  Per run of quads that are not
-            // predicted ONE ordered 16-bit store under an exec mask (each writes H[its context] = its hash, cheetah.rs:72,81,90; the first
-            // one's context is the running one, patched into its lane), per predicted quad one LDS round trip (:97-102).
-            // (v_writelane takes its lane from M0: an SGPR value and an SGPR lane select in one instruction break gfx9's one-scalar rule)
-            // State in the loop: `c2` = LDS address of H[running context]; `av` = per lane the LDS address of H[its context] (2 * hash of the quad
-            // before it, patched where the context is the running one) — the store's address operand and, shifted back, the context to report.
-            uint32_t av = lds0 + 2u * hprev;
-            const uint32_t h2 = lds0 + 2u * h;                                      // what the running context becomes behind a quad that is not predicted
-            uint64_t prem = P;
-            uint32_t c2 = lds0 + 2u * c;
-            uint32_t s_pos, s_p, s_r, v_t, v_u, s_m0;
-            uint64_t s_m;
-            asm volatile(
-                "s_mov_b32 %[m0s], m0\n\t"                                            // (M0 is the compiler's: handed back as found)
-                "s_mov_b32 %[pos], 0\n"
-                "1:\n\t"                                                             // ---- next run of quads that are not predicted: [pos, p)
-                "s_ff1_i32_b64 %[p], %[prem]\n\t"
-                "s_min_u32 %[p], %[p], 64\n\t"                                       // (no predicted quad left: -1 -> 64)
-                "s_sub_u32 %[r], %[p], %[pos]\n\t"
-                "s_cmp_eq_u32 %[r], 0\n\t"
-                "s_cbranch_scc1 2f\n\t"
-                "s_bfm_b64 %[m], %[r], %[pos]\n\t"                                   // r bits from pos on (r < 64: some quad is predicted)
-                "s_mov_b32 m0, %[pos]\n\t"
-                "s_add_u32 %[r], %[p], -1\n\t"
-                "v_writelane_b32 %[av], %[c2], m0\n\t"
-                "s_mov_b64 exec, %[m]\n\t"
-                "ds_write_b16 %[av], %[h]\n\t"
-                "s_mov_b64 exec, -1\n\t"
-                "v_readlane_b32 %[c2], %[h2], %[r]\n"
-                "2:\n\t"
-                "s_cmp_ge_u32 %[p], 64\n\t"
-                "s_cbranch_scc1 4f\n\t"
-                "v_mov_b32 %[t], %[c2]\n"
-                // ---- a predicted quad at lane p: c <- H[c] (cheetah.rs:97-102).  Round 4: the chain is the read, one add and the branch — ~85 cycles
-                // instead of ~105.  The address of H[c] (`t`, the same in every lane) goes into lane p's `av` by a select under a one-lane mask, the
-                // bookkeeping and the test "is the next quad predicted too" are issued while the read is in flight (its answer lands in `u`, so `t`
-                // stays readable), and the scalar copy of the context is taken once per run instead of once per quad.
-                "3:\n\t"
-                "ds_read_u16 %[u], %[t]\n\t"
-                "s_bfm_b64 %[m], 1, %[p]\n\t"
-                "s_bitset0_b64 %[prem], %[p]\n\t"
-                "s_add_u32 %[p], %[p], 1\n\t"
-                "v_cndmask_b32_e64 %[av], %[av], %[t], %[m]\n\t"
-                "s_bitcmp1_b64 %[prem], %[p]\n\t"                                    // (p == 64 tests bit 0, which is clear by now: lane 0 was either not predicted or has been taken)
-                "s_waitcnt lgkmcnt(0)\n\t"
-                "v_lshl_add_u32 %[t], %[u], 1, %[lds0]\n\t"
-                "s_cbranch_scc1 3b\n\t"
-                "s_nop 0\n\t"
-                "v_readfirstlane_b32 %[c2], %[t]\n\t"
-                "s_cmp_ge_u32 %[p], 64\n\t"
-                "s_cbranch_scc1 4f\n\t"
-                "s_mov_b32 %[pos], %[p]\n\t"
-                "s_branch 1b\n"
-                "4:\n\t"
-                "s_mov_b32 m0, %[m0s]\n\t"
-                : [av] "+v"(av), [c2] "+s"(c2), [prem] "+s"(prem), [pos] "=&s"(s_pos), [p] "=&s"(s_p), [r] "=&s"(s_r), [m] "=&s"(s_m), [t] "=&v"(v_t), [u] "=&v"(v_u), [m0s] "=&s"(s_m0)
-                : [h] "v"(hw), [h2] "v"(h2), [lds0] "s"(lds0)
-                : "memory", "scc");
-            c = (c2 - lds0) >> 1;
-            cv = (av - lds0) >> 1;
-        } else {
-            // a block with quads that take no part (a raw-copy block's, the chunk's end): the same, run by run, stepping over them — the
-            // context passes through (codec.rs:89-91: a raw block touches no state)
-            cv = 0;
-            uint32_t pos = 0;
-            while (pos < 64u) {
-                const uint64_t rest = active >> pos;
-                if (!rest) break;
-                pos += (uint32_t)__builtin_ctzll(rest);
-                if ((N >> pos) & 1ull) {
-                    const uint64_t inv = ~(N >> pos);
-                    const uint32_t r = inv ? (uint32_t)__builtin_ctzll(inv) : 64u - pos;
-                    const bool in = lane >= pos && lane < pos + r;
-                    const uint32_t mine = lane == pos ? c : hprev;
-                    if (in) {
-                        cv = mine;
-                        asm volatile("ds_write_b16 %0, %1" ::"v"(lds0 + 2u * mine), "v"(hw) : "memory");
-                    }
-                    c = (uint32_t)__builtin_amdgcn_readlane((int)h, (int)(pos + r - 1u));
-                    pos += r;
-                } else {
-                    const uint64_t inv = ~(P >> pos);
-                    const uint32_t r = inv ? (uint32_t)__builtin_ctzll(inv) : 64u - pos;
-                    for (uint32_t t = 0; t < r; ++t) {
-                        if (lane == pos + t) cv = c;
-                        uint32_t nx;
-                        asm volatile("ds_read_u16 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(nx) : "v"(lds0 + 2u * c) : "memory");
-                        nx = rfl(nx);
-                        if (nx == c) {                                             // a fixed point: the table does not change inside a run
-                            if (lane > pos + t && lane < pos + r) cv = c;
-                            break;
-                        }
-                        c = nx;
-                    }
-                    pos += r;
-                }
-            }
-        }
-        const uint32_t i = blk * 64u + lane;
-        if (i < nsteps) ctx[i] = (uint16_t)cv;
-    }
-    (void)val;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// walk, by a TEAM of waves (round 6; the default).  One wave spends its time ISSUING: ~380 instructions per 128 quads at one instruction per five cycles —
-// classification, the speculative reads level by level, the bookkeeping — and only ~500 cycles of those 2,500 in what must happen in stream order (the ordered
-// pass over H and its verification).  So kTeam waves of one work-group share the chunk's H: wave w takes the groups g = w (mod kTeam) of 128 quads, does
-// everything that needs no order AHEAD of its turn — its descriptors come straight from memory into registers two turns ahead, the speculative reads see H
-// as it stands, groups of other waves not yet applied: speculation may be as stale as it likes, the verification below does not care how a context was
-// guessed — and then, holding the token (an LDS word: the group whose turn it is; the running context travels beside it):
-//   patch      lane 0's context, if the quad before the group was predicted (its hash is the predecessor's to tell);
-//   execute    the ordered pass (as above), verify, take back and go again from the first wrong read until every lane stands;
-//   hand on    the running context and the token; the contexts are stored behind that.
-// Groups the 128-at-a-time form does not take (a raw-copy block, the chunk's end, a run of eight predicted quads) are walked block by block under the token
-// by the run-by-run code.  A wave's LDS operations execute in issue order and the token is written behind them: whoever sees it sees H after them (§4.2).
-// ---------------------------------------------------------------------------------------------------------------
-// (geometry, as compile-time switches for same-box A/B builds — tools/build_variant.sh, tools/gpu_walk_ab.py: waves of a team, blocks of 64 quads a turn, how
-// many turns ahead of its own a wave starts its speculative reads.  Measured on config 3, decode ms: 2 x 4 waves, one turn ahead 1.207; 1 x 4 1.205; 2 x 3 1.208;
-// 2 x 2 1.29; 4 x 4 1.39; 2 x 6 1.23; 2 x 4 reading as early as it can — three turns ahead — 1.33)
-#ifndef DENSITY_WALK_TEAM
-#define DENSITY_WALK_TEAM 4
-#endif
-#ifndef DENSITY_WALK_G
-#define DENSITY_WALK_G 2
-#endif
-#ifndef DENSITY_WALK_JIT
-#define DENSITY_WALK_JIT 1
-#endif
-constexpr uint32_t kTeam = DENSITY_WALK_TEAM, kTeamLds = kWalkTable + 64;
-template <uint32_t G>
-__global__ __launch_bounds__(kTeam * 64) void cheetah_walk_team(PassArgs a) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = rfl(threadIdx.x >> 6);
-    const uint64_t chunk = blockIdx.x;
-    const ChunkInfo ci = a.info[chunk];
-    if (ci.bad) return;
-    const uint32_t nsteps = ci.blocks * kRecQuads;
-    const uint32_t nblk = (nsteps + 63u) / 64u;
-    const uint32_t ngroups = (nblk + G - 1u) / G;
-    const uint64_t s0 = chunk * (a.out_stride / 4);
-    const uint32_t* __restrict__ desc = a.desc + s0;
-    uint16_t* __restrict__ ctx = a.ctx + s0;
-    {   // H starts as the hash of the reference's zeroed prediction table: hash(0) = 0; token 0, running context 0 (cheetah.rs:52)
-        uint4* p = reinterpret_cast<uint4*>(pass_lds);
-        for (uint32_t i = threadIdx.x; i < kTeamLds / 16; i += kTeam * 64) p[i] = make_uint4(0, 0, 0, 0);
-        __syncthreads();
-    }
-    const uint32_t lds0 = lds_addr(pass_lds);
-    const uint32_t token = lds0 + kWalkTable;                                       // {the group whose turn it is, the running context in front of it}: one 8-byte word
-    uint32_t nd[G], nprev = 0;
-    auto fetch = [&](uint32_t g) {
-#pragma unroll
-        for (uint32_t b = 0; b < G; ++b) {
-            const uint32_t i = (g * G + b) * 64u + lane;
-            nd[b] = i < nsteps ? desc[i] : kDescNone;
-        }
-        nprev = g ? desc[g * G * 64u - 1u] : 0u;                                      // the quad in front of the group
-    };
-    if (wave < ngroups) fetch(wave);
-    for (uint32_t g = wave; g < ngroups; g += kTeam) {
-        const uint32_t blk = g * G;
-        uint32_t dv[G], hv[G], hwv[G], cvv[G], rsv[G], rfv[G], r2v[G], shv[G];
-        uint64_t Pm[G], Nm[G], K0m[G], known[G], fin[G], rdone[G];
-        const uint32_t dprev = rfl(nprev);
-        bool ok = blk + G <= nblk;
-#pragma unroll
-        for (uint32_t b = 0; b < G; ++b) {
-            dv[b] = nd[b];
-            hv[b] = dv[b] & 0xffffu;
-            hwv[b] = (dv[b] & kDescZero) ? 0u : hv[b];
-            const bool none = (dv[b] & kDescNone) != 0, pred = ((dv[b] >> 16) & 3u) == kFlagPred;
-            Pm[b] = ballot64(!none && pred); Nm[b] = ballot64(!none && !pred);
-            uint64_t lr = Pm[b] & (Pm[b] >> 1); lr &= lr >> 2; lr &= lr >> 4;
-            ok = ok && (Pm[b] | Nm[b]) == ~0ull && lr == 0;
-        }
-        if (g + kTeam < ngroups) fetch(g + kTeam);                                    // in flight across this turn
-        // the context in front of the group, where the descriptors tell it: the hash of a quad that took part and was not predicted
-        const bool c_known = g == 0 || (!(dprev & kDescNone) && ((dprev >> 16) & 3u) != kFlagPred);
-        const uint32_t c_spec = g == 0 ? 0u : (dprev & 0xffffu);
-        // speculate: every level's reads of all G blocks in flight together (lanes whose context is known and who have not read yet)
-        auto speculate = [&]() __attribute__((always_inline)) {
-            for (;;) {
-                uint64_t R[G], any = 0;
-#pragma unroll
-                for (uint32_t b = 0; b < G; ++b) { R[b] = Pm[b] & known[b] & ~rdone[b]; any |= R[b]; }
-                if (!any) break;
-                uint32_t r[G], ad[G];
-#pragma unroll
-                for (uint32_t b = 0; b < G; ++b) ad[b] = lds0 + 2u * cvv[b];
-                lds_read_u16_group<G>(r, ad);                                          // (every block reads, whether or not one of its lanes needs it: a stale context is a valid address)
-#pragma unroll
-                for (uint32_t b = 0; b < G; ++b) {
-                    const uint64_t in = (R[b] << 1) | (b == 0 ? 0ull : (R[b ? b - 1 : 0] >> 63));   // the lanes that learn their context this round
-                    if (R[b]) rsv[b] = msel(R[b], r[b], rsv[b]);
-                    if (in) {
-                        uint32_t up = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r[b], 0x138, 0xf, 0xf, false);   // wave_shr:1
-                        if (b != 0 && (in & 1ull)) { const uint32_t carry = (uint32_t)__builtin_amdgcn_readlane((int)r[b ? b - 1 : 0], 63); up = lane == 0 ? carry : up; }
-                        cvv[b] = msel(in, up, cvv[b]);
-                    }
-                    known[b] |= in; rdone[b] |= R[b];
-                }
-            }
-        };
-        // the ordered pass's operands: made AHEAD of the turn too (only a patched lane 0 or a wrong read makes them again)
-        uint32_t xa[G], xm[G], xv[G];
-        auto prepare_exec = [&]() __attribute__((always_inline)) {
-#pragma unroll
-            for (uint32_t b = 0; b < G; ++b) {
-                shv[b] = (cvv[b] & 1u) * 16u;
-                const uint64_t w = Nm[b] & ~fin[b];
-                xa[b] = lds0 + ((2u * cvv[b]) & ~3u);
-                xm[b] = msel(w, 0xffffu << shv[b], 0u); xv[b] = msel(w, hwv[b] << shv[b], 0u);
-            }
-        };
-        if (ok) {
-#pragma unroll
-            for (uint32_t b = 0; b < G; ++b) {
-                const uint32_t hp = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hv[b], 0x138, 0xf, 0xf, false);   // wave_shr:1
-                const uint32_t first = b == 0 ? c_spec : (uint32_t)__builtin_amdgcn_readlane((int)hv[b ? b - 1 : 0], 63);   // (meaningful only where the quad before was not predicted)
-                cvv[b] = lane == 0 ? first : hp;
-                K0m[b] = (Nm[b] << 1) | (b == 0 ? (c_known ? 1ull : 0ull) : (Nm[b ? b - 1 : 0] >> 63));
-                known[b] = K0m[b]; fin[b] = 0; rsv[b] = 0; rfv[b] = 0; rdone[b] = 0;
-            }
-            if (DENSITY_WALK_JIT && g >= DENSITY_WALK_JIT) {                              // not before my turn is DENSITY_WALK_JIT turns away: what is read earlier is stale more often than not
-                for (uint32_t spins = 0; spins < kSpinLimit; ++spins) {
-                    uint32_t seen;
-                    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(seen) : "v"(token) : "memory");
-                    seen = rfl(seen);
-                    if (seen + DENSITY_WALK_JIT >= g) break;
-                }
-            }
-            speculate();                                                              // AHEAD of my turn: H as it stands
-            prepare_exec();
-        }
-        // ---- my turn ----
-        uint32_t c;
-        {
-            bool poisoned = false;
-            for (uint32_t spins = 0;; ++spins) {
-                uint64_t tc;
-                asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(tc) : "v"(token) : "memory");
-                const uint32_t seen = rfl((uint32_t)tc);
-                if (seen == g) { c = rfl((uint32_t)(tc >> 32)); break; }
-                if (seen == kPoison || spins > kSpinLimit) {
-                    if (seen != kPoison && lane == 0) { atomicOr(a.err, kErrWatchdog); *reinterpret_cast<volatile uint32_t*>(pass_lds + kWalkTable) = kPoison; }
-                    poisoned = true;
-                    break;
-                }
-            }
-            if (poisoned) break;
-        }
-        if (ok) {
-            if (!c_known) {                                                          // the predecessor's last quad was predicted (or took no part): its hash is what the predecessor says
-                cvv[0] = lane == 0 ? c : cvv[0];
-                K0m[0] |= 1ull; known[0] |= 1ull;
-                speculate();                                                          // (what lane 0's context sets free)
-                prepare_exec();
-            }
-            for (;;) {
-                // execute: the lanes that do not stand yet, block after block, each in lane order
-                uint32_t ret[G];
-                lds_mskor_group<G>(ret, xa, xm, xv);
-                // verify
-                uint64_t bad[G], anybad = 0;
-#pragma unroll
-                for (uint32_t b = 0; b < G; ++b) {
-                    r2v[b] = (ret[b] >> shv[b]) & 0xffffu;
-                    // a predicted lane that has not read at all yet (its context never became known: cannot happen once lane 0's is) counts as wrong
-                    bad[b] = (ballot64(r2v[b] != rsv[b]) | ~rdone[b]) & Pm[b] & ~fin[b];
-                    anybad |= bad[b];
-                }
-                if (__builtin_expect(anybad == 0, 1)) {
-#pragma unroll
-                    for (uint32_t b = 0; b < G; ++b) rfv[b] = msel(~fin[b], r2v[b], rfv[b]);
-                    break;
-                }
-                uint32_t b0 = 0;
-#pragma unroll
-                for (uint32_t b = G; b-- > 0;) if (bad[b]) b0 = b;
-                uint64_t badb = bad[0];
-#pragma unroll
-                for (uint32_t b = 1; b < G; ++b) badb = b0 == b ? bad[b] : badb;
-                const uint32_t i0 = (uint32_t)__builtin_ctzll(badb);
-                const uint64_t upto = (2ull << i0) - 1ull;                           // lanes 0 .. i0 of block b0 (i0 == 63: all of them)
-                uint64_t stands[G];
-#pragma unroll
-                for (uint32_t b = 0; b < G; ++b) stands[b] = b < b0 ? ~0ull : b == b0 ? upto : 0ull;
-                // the writes behind the first wrong read are taken back: old halves, the latest write first (blocks from the last to b0, lanes reversed)
-#pragma unroll
-                for (uint32_t b = G; b-- > 0;) {
-                    const uint64_t undo = Nm[b] & ~stands[b] & ~fin[b];
-                    if (undo) {
-                        const uint32_t ar = bperm(63u - lane, lds0 + 2u * cvv[b]), old = bperm(63u - lane, r2v[b]);
-                        if ((undo >> (63u - lane)) & 1ull) asm volatile("ds_write_b16 %0, %1" ::"v"(ar), "v"(old) : "memory");
-                    }
-                }
-                const uint32_t truth = (uint32_t)__builtin_amdgcn_readlane((int)(b0 == 0 ? r2v[0] : b0 == 1 ? r2v[G > 1 ? 1 : 0] : b0 == 2 ? r2v[G > 2 ? 2 : 0] : r2v[G > 3 ? 3 : 0]), (int)i0);
-                bool all = true;
-                uint64_t nextm[G];
-#pragma unroll
-                for (uint32_t b = 0; b < G; ++b) {
-                    rfv[b] = msel(stands[b] & ~fin[b], r2v[b], rfv[b]);
-                    fin[b] = stands[b];
-                    all = all && fin[b] == ~0ull;
-                    // the lane behind (b0, i0) now knows its context; everything else behind it is as unknown as before the first round
-                    const uint64_t next = b == b0 ? (i0 == 63u ? 0ull : (2ull << i0) & ~upto) : (b == b0 + 1u && i0 == 63u ? 1ull : 0ull);
-                    if (next) cvv[b] = msel(next, truth, cvv[b]);
-                    nextm[b] = next;
-                }
-                if (all) break;
-                // What has to be guessed again is the CHAIN behind the wrong read — the lane that now knows its context, the run of predicted lanes it starts
-                // and the lane behind that run —, not the block: every other lane's context and speculative read are as good a guess as they were, and the
-                // next verification holds all of them to the ordered pass again.  (A chain that runs on into the next block: everything behind the wrong read, as before.)
-                const uint32_t cb = i0 == 63u ? b0 + 1u : b0, start = i0 == 63u ? 0u : i0 + 1u;
-                uint64_t pcb = Pm[0];
-#pragma unroll
-                for (uint32_t b = 1; b < G; ++b) pcb = cb == b ? Pm[b] : pcb;
-                const uint64_t inv = ~(pcb >> start);
-                const uint32_t end = start + (inv ? (uint32_t)__builtin_ctzll(inv) : 64u);   // the lane behind the run (the chain's last)
-                if (end <= 63u) {
-                    const uint64_t A = ((2ull << end) - 1ull) & ~((1ull << start) - 1ull);
-#pragma unroll
-                    for (uint32_t b = 0; b < G; ++b)
-                        if (b == cb) { known[b] = (known[b] & ~A) | nextm[b]; rdone[b] &= ~A; }
-                } else {
-#pragma unroll
-                    for (uint32_t b = 0; b < G; ++b) { known[b] = fin[b] | nextm[b] | K0m[b]; rdone[b] = fin[b]; }
-                }
-                speculate();
-                prepare_exec();
-            }
-            const uint32_t last = msel(Pm[G - 1], rfv[G - 1], hv[G - 1]);
-            c = (uint32_t)__builtin_amdgcn_readlane((int)last, 63);
-        } else {
-            // block by block, run by run (cheetah.rs:97-102; raw-copy blocks and quads beyond the end take no part: the context passes through)
-            auto one_block = [&](auto bc) __attribute__((always_inline)) {                                           // (written out per block: left as a loop over b the compiler keeps it rolled and the masks in vector registers)
-                constexpr uint32_t b = decltype(bc)::value;
-                if (blk + b >= nblk) { cvv[b] = 0; return; }
-                const uint32_t h = hv[b], hw = hwv[b];
-                const uint64_t P = Pm[b], N = Nm[b], active = P | N;
-                const uint32_t hprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)h, 0x138, 0xf, 0xf, false);   // wave_shr:1
-                if (active == ~0ull && P != 0 && P != ~0ull) {                        // every quad takes part, some are predicted: the hand-written chain (see cheetah_walk)
-                    cvv[b] = walk_chain_block(lds0, c, hprev, h, hw, P);
-                    return;
-                }
-                uint32_t cv = 0, pos = 0;
-                while (pos < 64u) {
-                    const uint64_t rest = active >> pos;
-                    if (!rest) break;
-                    pos += (uint32_t)__builtin_ctzll(rest);
-                    if ((N >> pos) & 1ull) {
-                        const uint64_t inv = ~(N >> pos);
-                        const uint32_t r = inv ? (uint32_t)__builtin_ctzll(inv) : 64u - pos;
-                        const bool in = lane >= pos && lane < pos + r;
-                        const uint32_t mine = lane == pos ? c : hprev;
-                        if (in) {
-                            cv = mine;
-                            asm volatile("ds_write_b16 %0, %1" ::"v"(lds0 + 2u * mine), "v"(hw) : "memory");
-                        }
-                        c = (uint32_t)__builtin_amdgcn_readlane((int)h, (int)(pos + r - 1u));
-                        pos += r;
-                    } else {
-                        const uint64_t inv = ~(P >> pos);
-                        const uint32_t r = inv ? (uint32_t)__builtin_ctzll(inv) : 64u - pos;
-                        for (uint32_t t = 0; t < r; ++t) {
-                            if (lane == pos + t) cv = c;
-                            uint32_t nx;
-                            asm volatile("ds_read_u16 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(nx) : "v"(lds0 + 2u * c) : "memory");
-                            nx = rfl(nx);
-                            if (nx == c) {                                             // a fixed point: the table does not change inside a run
-                                if (lane > pos + t && lane < pos + r) cv = c;
-                                break;
-                            }
-                            c = nx;
-                        }
-                        pos += r;
-                    }
-                }
-                cvv[b] = cv;
-            };
-            one_block(std::integral_constant<uint32_t, 0>{});
-            if constexpr (G > 1) one_block(std::integral_constant<uint32_t, 1>{});
-            if constexpr (G > 2) { one_block(std::integral_constant<uint32_t, 2>{}); one_block(std::integral_constant<uint32_t, 3>{}); }
-        }
-        // hand on: the token and the running context in one 8-byte write, behind everything this turn did to H (a wave's LDS operations execute as issued)
-        {
-            const uint64_t tc = (uint64_t)(g + 1u) | ((uint64_t)c << 32);
-            asm volatile("ds_write_b64 %0, %1" ::"v"(token), "v"(tc) : "memory");
-        }
-#pragma unroll
-        for (uint32_t b = 0; b < G; ++b) { const uint32_t i = (blk + b) * 64u + lane; if (i < nsteps) ctx[i] = (uint16_t)cvv[b]; }
-    }
-}
-
 }  // namespace
+}  // namespace density
+
+// The walk is a file of its own, compiled HERE, as part of this translation unit (what it needs of the above it names as it stands; a unit of its
+// own would be free to allocate the passes' and the walk's registers differently: see rotor.hip on its kernel files).
+#include "decode_walk.hip"
+
+namespace density {
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side
@@ -1464,11 +751,7 @@ hipError_t launch_decode_passes(int algo, const uint8_t* d_in, const uint64_t* d
     const uint32_t blocks_per_chunk = (uint32_t)(out_stride / kRecBytes);
     hipError_t e = hipFuncSetAttribute((const void*)cheetah_pass<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pass_lds_bytes(1));
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)cheetah_pass<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pass_lds_bytes(2));
-    // the walk: a team of four waves, 128 quads a turn (default); g_walk_blocks 1 / 4: ONE wave, 64 / 128 quads at a time; g_chain_walk: one wave, run by run
-    const bool team = !g_chain_walk && g_walk_blocks == 2;
-    auto walk = g_chain_walk ? cheetah_walk<0> : g_walk_blocks == 1 ? cheetah_walk<1> : cheetah_walk<2>;
-    if (e == hipSuccess) e = team ? hipFuncSetAttribute((const void*)cheetah_walk_team<DENSITY_WALK_G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTeamLds)
-                                  : hipFuncSetAttribute((const void*)walk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWalkLds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)cheetah_walk_team, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTeamLds);
     if (e != hipSuccess) return e;
     // the records of calm stretches are found by the window kernels (their tables live where the descriptors and contexts will: nothing else is in use yet)
     const uint64_t slot_bound = out_stride + out_stride / kRecBytes * kSigBytes + kSigBytes;
@@ -1493,8 +776,7 @@ hipError_t launch_decode_passes(int algo, const uint8_t* d_in, const uint64_t* d
     const uint64_t pairs = (uint64_t)n_chunks * (blocks_per_chunk / 2);
     hipLaunchKernelGGL(cheetah_prepare, dim3((uint32_t)((pairs + 3) / 4)), dim3(256), 0, stream, a, blocks_per_chunk);
     hipLaunchKernelGGL(cheetah_pass<1>, dim3(4 * n_chunks), dim3(kPassWaves * 64), pass_lds_bytes(1), stream, a);
-    if (team) hipLaunchKernelGGL(cheetah_walk_team<DENSITY_WALK_G>, dim3(n_chunks), dim3(kTeam * 64), kTeamLds, stream, a);
-    else hipLaunchKernelGGL(walk, dim3(n_chunks), dim3(64), kWalkLds, stream, a);
+    hipLaunchKernelGGL(cheetah_walk_team, dim3(n_chunks), dim3(kTeam * 64), kTeamLds, stream, a);
     hipLaunchKernelGGL(cheetah_pass<2>, dim3(2 * n_chunks), dim3(kPassWaves * 64), pass_lds_bytes(2), stream, a);
     hipLaunchKernelGGL(cheetah_finish, dim3((n_chunks + 255) / 256), dim3(256), 0, stream, a, exact ? 1u : 0u, d_produced);
     return hipGetLastError();

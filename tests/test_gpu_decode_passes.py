@@ -1,5 +1,5 @@
 """Cheetah container decode in passes (density_amd/csrc/decode_passes.hip: records parsed per chunk, dictionary and prediction tables as
-ordered LDS exchange passes, the chain of contexts on one wave per chunk) against the oracle: containers ASSEMBLED ON THE CPU from oracle
+ordered LDS exchange passes, the chain of contexts by a team of four waves per chunk) against the oracle: containers ASSEMBLED ON THE CPU from oracle
 streams — so nothing the GPU encoder does can mask a decoder fault — decode to the input bit for bit; the one-wave decoder (kernel variant
 128) must agree, error for error."""
 import struct
@@ -121,6 +121,24 @@ def test_the_passes_run():
     assert (c1 - c0, c2 - c1) == (1, 0)
     small, _ = cpu_container(data[:20000], 4096)                                          # chunks below 64 KiB: the one-wave decoder
     assert container.decode(small, out) == 20000 and lib.density_hip_decode_pass_count() == c2
+
+
+def test_reserved_walk_bits_select_nothing():
+    """Kernel-variant bits 4096, 8192 and 16384 selected one-wave forms of the contexts walk, which are gone: the bits are reserved — accepted, and the
+    passes serve the decode as they do under variant 0 (three chunks of 256 blocks each, the smallest chunk the passes take)."""
+    from density_amd import _lib
+    lib = _lib.lib()
+    data = make("prose", 3 * 65536 + 5, seed=2)
+    raw, _ = cpu_container(data, 65536)
+    try:
+        for variant in (0, 4096, 8192, 16384, 4096 | 8192 | 16384):
+            container.set_kernel_variant(variant)
+            out = np.zeros(data.size, dtype=np.uint8)
+            before = lib.density_hip_decode_pass_count()
+            assert container.decode(raw, out) == data.size and np.array_equal(out, data), variant
+            assert lib.density_hip_decode_pass_count() - before == 1, variant
+    finally:
+        container.set_kernel_variant(0)
 
 
 @pytest.mark.parametrize("kind", ["prose", "mixed", "pairs"])

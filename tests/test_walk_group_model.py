@@ -1,4 +1,4 @@
-"""The grouped contexts walk of Cheetah's decode passes (density_amd/csrc/decode_passes.hip::cheetah_walk<NB>: speculate by reads, ONE ordered pass over the group,
+"""The grouped contexts walk of Cheetah's decode passes (density_amd/csrc/decode_walk.hip::cheetah_walk_team: speculate by reads, ONE ordered pass over the group,
 verify, take back, go again) as restated in tools/walk_group_model.py must give the sequential walk's contexts, running context and table (cheetah.rs:72,81,90,
 97-102) on descriptor streams built to collide: few hashes, many predicted quads, reads of never-written contexts."""
 import os

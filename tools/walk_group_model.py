@@ -1,5 +1,5 @@
-"""The grouped contexts walk of decode_passes.hip::cheetah_walk<NB> (speculate by reads, one ordered pass, verify, take back, go again) and the turn of its team
-form cheetah_walk_team (speculative reads ahead of the turn against a stale table, lane 0 patched under the token, a wrong read costs its chain) restated in Python and held
+"""The grouped contexts walk of Cheetah's decode passes (speculate by reads, one ordered pass, verify, take back, go again: one turn of decode_walk.hip::cheetah_walk_team
+without its team) and the turn of the team form itself (speculative reads ahead of the turn against a stale table, lane 0 patched under the token, a wrong read costs its chain) restated in Python and held
 against the sequential walk (cheetah.rs:72,81,90,97-102 on hashes) on adversarial descriptor streams.  tests/test_walk_group_model.py runs it."""
 import random
 
@@ -96,7 +96,7 @@ def grouped(pred, h, hw, c0, H, G=2, L=64):
 
 
 def team_turn(pred, h, hw, c_in, H, H_stale, c_known, G=2, L=64):
-    """One turn of decode_passes.hip::cheetah_walk_team (round 6): the speculative reads happen AHEAD of the turn against `H_stale` (H as some earlier moment left
+    """One turn of decode_walk.hip::cheetah_walk_team (round 6): the speculative reads happen AHEAD of the turn against `H_stale` (H as some earlier moment left
     it — other waves' turns not yet applied; anything at all would do), with lane 0's context taken from the descriptors if `c_known` and left open otherwise;
     under the token: lane 0 patched with the running context `c_in`, what that sets free read from the real H, the ordered pass, the verification; behind a
     wrong read only its CHAIN is guessed again (the lane that now knows its context, the run of predicted lanes it starts, the lane behind that run) unless the
