@@ -19,14 +19,20 @@ extern "C" {
 }
 
 /// include/density_hip.h section 2, sealed containers (DENSITY_HIP_FLAG_CHECKSUM): what a CPU reader and a host-pointer producer link.  The device-pointer calls
-/// (density_hip_checksum_device, density_hip_seal_device, density_hip_decode_device_verdicts) take a hipStream_t and belong to a caller that already binds HIP; they are declared here in step with the header.
+/// (density_hip_checksum_device, density_hip_seal_device, density_hip_decode_device_verdicts, density_hip_parity_device, density_hip_decode_device_recover) take a hipStream_t and belong to a caller that already binds HIP; they are declared here in step with the header.
 pub mod sealed {
     pub const DENSITY_HIP_FLAG_CHECKSUM: u16 = 8;
     pub const DENSITY_HIP_ERR_CHECKSUM: i32 = 6;
     pub const DENSITY_HIP_CHUNK_DAMAGED: u32 = 1;
     pub const DENSITY_HIP_SALVAGE_BLANK: u32 = 1;
+    pub const DENSITY_HIP_CHUNK_RECOVERED: u32 = 2;
+    pub const DENSITY_HIP_PARITY_MAGIC: u32 = 0x31504844;
     #[repr(C)]
     pub struct DensityHipHeader { pub magic: u32, pub algo: u8, pub version: u8, pub flags: u16, pub chunk_size: u32, pub n_chunks: u32, pub total_len: u64, pub container_len: u64 }
+    /// the first 32 bytes of a parity blob "DHP1": n_groups rows of row_bytes bytes follow, row g the XOR of the input chunks i with i % n_groups == g
+    #[repr(C)]
+    pub struct DensityHipParityHeader { pub magic: u32, pub version: u8, pub reserved0: u8, pub reserved1: u16, pub chunk_size: u32, pub n_chunks: u32, pub total_len: u64,
+                                        pub n_groups: u32, pub row_bytes: u32 }
     #[link(name = "density_hip")]
     extern "C" {
         /// C of one decoded chunk, host arithmetic (no device): compare with trailer entry i at container_len - round_up(4 * n_chunks, 16) + 4 * i
@@ -43,6 +49,18 @@ pub mod sealed {
                                                   d_verdicts: *mut u32, flags: core::ffi::c_uint, damaged_out: *mut u32) -> i32;
         pub fn density_hip_decode_verdicts(container: *const u8, container_size: usize, output: *mut u8, output_size: usize, verdicts: *mut u32,
                                            verdict_capacity: usize, flags: core::ffi::c_uint, damaged_out: *mut u32) -> usize;
+        /// recovery records: the parity blob of an input (a sidecar: no container holds it), and the verdict decode that rebuilds every chunk that is the only
+        /// damaged one of its group (verdict DENSITY_HIP_CHUNK_RECOVERED); d_parity: device; parity_header, damaged_out, recovered_out: host, each optional.
+        pub fn density_hip_parity_size(input_size: usize, chunk_size: usize, n_groups: u32) -> usize;
+        pub fn density_hip_parity_device(d_input: *const core::ffi::c_void, input_size: usize, chunk_size: usize, n_groups: u32, d_parity: *mut core::ffi::c_void,
+                                         parity_capacity: usize, stream: *mut core::ffi::c_void) -> i32;
+        pub fn density_hip_parity(input: *const u8, input_size: usize, chunk_size: usize, n_groups: u32, parity: *mut u8, parity_capacity: usize) -> usize;
+        pub fn density_hip_decode_device_recover(d_container: *const core::ffi::c_void, container_size: usize, header: *const DensityHipHeader, d_parity: *const core::ffi::c_void,
+                                                 parity_size: usize, parity_header: *const DensityHipParityHeader, d_output: *mut core::ffi::c_void, output_capacity: usize,
+                                                 d_workspace: *mut core::ffi::c_void, workspace_size: usize, stream: *mut core::ffi::c_void, d_verdicts: *mut u32,
+                                                 flags: core::ffi::c_uint, damaged_out: *mut u32, recovered_out: *mut u32) -> i32;
+        pub fn density_hip_decode_recover(container: *const u8, container_size: usize, parity: *const u8, parity_size: usize, output: *mut u8, output_size: usize,
+                                          verdicts: *mut u32, verdict_capacity: usize, flags: core::ffi::c_uint, damaged_out: *mut u32, recovered_out: *mut u32) -> usize;
     }
 }
 

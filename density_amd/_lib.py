@@ -15,7 +15,9 @@ DEFAULT_CHUNK = 1 << 20
 
 OK, ERR_ARGUMENT, ERR_CAPACITY, ERR_FORMAT, ERR_RUNTIME, ERR_UNSUPPORTED, ERR_CHECKSUM = range(7)
 CHUNK_DAMAGED = 1       # DENSITY_HIP_CHUNK_DAMAGED: a verdict word
+CHUNK_RECOVERED = 2     # DENSITY_HIP_CHUNK_RECOVERED: a verdict word of the recover calls
 SALVAGE_BLANK = 1       # DENSITY_HIP_SALVAGE_BLANK: flags of the verdict calls
+PARITY_MAGIC = 0x31504844   # "DHP1"
 
 
 class Header(ctypes.Structure):
@@ -23,6 +25,13 @@ class Header(ctypes.Structure):
     _fields_ = [("magic", ctypes.c_uint32), ("algo", ctypes.c_uint8), ("version", ctypes.c_uint8), ("flags", ctypes.c_uint16),
                 ("chunk_size", ctypes.c_uint32), ("n_chunks", ctypes.c_uint32), ("total_len", ctypes.c_uint64),
                 ("container_len", ctypes.c_uint64)]
+
+
+class ParityHeader(ctypes.Structure):
+    """density_hip_parity_header_t"""
+    _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint8), ("reserved0", ctypes.c_uint8), ("reserved1", ctypes.c_uint16),
+                ("chunk_size", ctypes.c_uint32), ("n_chunks", ctypes.c_uint32), ("total_len", ctypes.c_uint64),
+                ("n_groups", ctypes.c_uint32), ("row_bytes", ctypes.c_uint32)]
 
 
 class Shard(ctypes.Structure):
@@ -72,6 +81,13 @@ SYMBOLS.update({
     "density_hip_seal_device": (_I, [_VP, _SZ, _VP, _SZ, ctypes.POINTER(Header), _VP, ctypes.POINTER(Header)]),
     "density_hip_decode_device_verdicts": (_I, [_VP, _SZ, ctypes.POINTER(Header), _VP, _SZ, _VP, _SZ, _VP, _VP, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint32)]),
     "density_hip_decode_verdicts": (_SZ, [_VP, _SZ, _VP, _SZ, ctypes.POINTER(ctypes.c_uint32), _SZ, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint32)]),
+    "density_hip_parity_size": (_SZ, [_SZ, _SZ, ctypes.c_uint32]),
+    "density_hip_parity_device": (_I, [_VP, _SZ, _SZ, ctypes.c_uint32, _VP, _SZ, _VP]),
+    "density_hip_parity": (_SZ, [_VP, _SZ, _SZ, ctypes.c_uint32, _VP, _SZ]),
+    "density_hip_decode_device_recover": (_I, [_VP, _SZ, ctypes.POINTER(Header), _VP, _SZ, ctypes.POINTER(ParityHeader), _VP, _SZ, _VP, _SZ, _VP, _VP, ctypes.c_uint,
+                                               ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    "density_hip_decode_recover": (_SZ, [_VP, _SZ, _VP, _SZ, _VP, _SZ, ctypes.POINTER(ctypes.c_uint32), _SZ, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint32),
+                                         ctypes.POINTER(ctypes.c_uint32)]),
     "density_hip_encode_workspace_size": (_SZ, [_I, _SZ, _SZ]),
     "density_hip_decode_workspace_size": (_SZ, [ctypes.c_uint32]),
     "density_hip_decode_workspace_size_for": (_SZ, [_I, _SZ, _SZ]),

@@ -8,9 +8,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdensity_hip.so")
 LIB_DEBUG = os.path.join(HERE, "libdensity_hip_debug.so")      # -DDENSITY_HIP_DEBUG: the only build that reads tuning / diagnostic switches from the environment
-SOURCES = ["api.hip", "api_stream.hip", "api_host.hip", "chameleon.hip", "rotor.hip", "container.hip", "checksum.hip", "serial_codec.hip", "stream_parse.hip", "exchange_stages.hip", "decode_passes.hip", "placement.hip"]
+SOURCES = ["api.hip", "api_stream.hip", "api_host.hip", "chameleon.hip", "rotor.hip", "container.hip", "checksum.hip", "parity.hip", "serial_codec.hip", "stream_parse.hip", "exchange_stages.hip", "decode_passes.hip", "placement.hip"]
 # what the sources include; rotor_encode.hip and rotor_decode.hip are included by rotor.hip, decode_walk.hip by decode_passes.hip (one translation unit each: see there)
-HEADERS = ["api_internal.hpp", "common.hpp", "chameleon_dev.hpp", "rotor_dev.hpp", "rotor_encode.hip", "rotor_decode.hip", "decode_walk.hip", "kernels.hpp", "checksum.hpp",
+HEADERS = ["api_internal.hpp", "common.hpp", "chameleon_dev.hpp", "rotor_dev.hpp", "rotor_encode.hip", "rotor_decode.hip", "decode_walk.hip", "kernels.hpp", "checksum.hpp", "checksum_dev.hpp",
            os.path.join("..", "..", "include", "density_hip.h")]
 
 

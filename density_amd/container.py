@@ -306,6 +306,72 @@ def decode_verdicts(container, output, blank=True):
     return r, bad
 
 
+def parity_size(input_size, chunk_size, n_groups):
+    """The exact size of the parity blob "DHP1" (include/density_hip.h) of input_size bytes cut every chunk_size bytes — the chunk size the container has, not
+    0 — with n_groups rows (at most one per chunk); 0 where the arguments are invalid."""
+    return int(_lib.lib().density_hip_parity_size(input_size, chunk_size, n_groups))
+
+
+def parse_parity_header(raw32):
+    """The header of a host-resident parity blob; raises DecodeError where it is not one."""
+    raw = bytes(raw32[:32])
+    if len(raw) < 32:
+        raise DecodeError("parity blob shorter than its header")
+    h = _lib.ParityHeader.from_buffer_copy(raw)
+    if h.magic != _lib.PARITY_MAGIC or h.version != 1:
+        raise DecodeError("not a parity blob (magic, version)")
+    return h
+
+
+def parity_device(d_in, n, chunk_size, n_groups, d_parity, cap, stream=0):
+    """Enqueue the parity blob of n bytes of device memory into d_parity (cap >= parity_size(); both at any alignment)."""
+    _check(_lib.lib().density_hip_parity_device(d_in, n, chunk_size, n_groups, d_parity, cap, stream), EncodeError)
+
+
+def parity(input, chunk_size, n_groups, output):
+    """The parity blob of a host-resident input into `output`; returns the bytes written."""
+    ia, n, k1 = _ro(input)
+    oa, cap, k2 = _rw(output)
+    r = _lib.lib().density_hip_parity(ia, n, chunk_size, n_groups, oa, cap)
+    if r == 0:
+        raise EncodeError(_lib.last_error())
+    return r
+
+
+def decode_device_recover(d_container, container_size, d_parity, parity_size, d_out, cap, d_verdicts, header=None, parity_header=None, stream=0, workspace=(0, 0),
+                          blank=True, sync=True):
+    """decode_device_verdicts, then every chunk that is the only damaged one of its parity group rebuilt from the blob at d_parity and verified again: its
+    verdict becomes _lib.CHUNK_RECOVERED.  Returns (return code, chunks still damaged, chunks recovered) — OK wherever nothing remains damaged, else
+    ERR_FORMAT or ERR_CHECKSUM, each with valid verdicts — or None with sync=False.  Anything else (an unsealed container, a blob that is not this
+    container's or is malformed, a capacity) raises DecodeError."""
+    damaged, recovered = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    rc = _lib.lib().density_hip_decode_device_recover(d_container, container_size, ctypes.byref(header) if header is not None else None, d_parity, parity_size,
+                                                      ctypes.byref(parity_header) if parity_header is not None else None, d_out, cap, workspace[0], workspace[1],
+                                                      stream, d_verdicts, _lib.SALVAGE_BLANK if blank else 0, ctypes.byref(damaged) if sync else None,
+                                                      ctypes.byref(recovered) if sync else None)
+    if rc not in (_lib.OK, _lib.ERR_CHECKSUM, _lib.ERR_FORMAT) or (rc == _lib.ERR_FORMAT and "chunks damaged" not in _lib.last_error()):
+        _check(rc, DecodeError)
+    return (rc, damaged.value, recovered.value) if sync else None
+
+
+def decode_recover(container, parity, output, blank=True):
+    """decode_verdicts with a parity blob: returns (bytes written, indices of the chunks still damaged, indices of the chunks recovered).  Raises ChecksumError
+    (damaged_chunks: all of them) where every chunk remains damaged, DecodeError for anything that is not damage."""
+    ia, n, k1 = _ro(container)
+    pa, pn, k3 = _ro(parity)
+    oa, cap, k2 = _rw(output)
+    nc = parse_header(ctypes.string_at(ia, 32)).n_chunks if n >= 32 else 0
+    verdicts = (ctypes.c_uint32 * max(nc, 1))()
+    damaged, recovered = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    r = _lib.lib().density_hip_decode_recover(ia, n, pa, pn, oa, cap, verdicts, nc, _lib.SALVAGE_BLANK if blank else 0, ctypes.byref(damaged), ctypes.byref(recovered))
+    bad = [i for i in range(nc) if verdicts[i] == _lib.CHUNK_DAMAGED] if damaged.value else []
+    if r == 0 and _lib.last_error():          # 0 with no error == a valid, empty container
+        if nc and damaged.value == nc:
+            raise ChecksumError(_lib.last_error(), damaged_chunks=bad)
+        raise DecodeError(_lib.last_error())
+    return r, bad, [i for i in range(nc) if verdicts[i] == _lib.CHUNK_RECOVERED] if recovered.value else []
+
+
 def stream_encode_device(algo, d_in, n, d_out, cap, stream=0):
     size = ctypes.c_size_t(0)
     _check(_lib.lib().density_hip_stream_encode_device(_lib.ALGO_IDS[algo], d_in, n, d_out, cap, stream, ctypes.byref(size)), EncodeError)

@@ -320,31 +320,51 @@ int run_decode_container(DeviceCtx* c, const uint8_t* d_in, size_t container_siz
 // workspace held against the trailer once more for a word per chunk and a count, then — with DENSITY_HIP_SALVAGE_BLANK — zeros over the damaged chunks.
 // damaged_out (host, nullable): synchronises; it is written wherever the verdicts are valid, a format error included.
 int run_decode_verdicts(DeviceCtx* c, const uint8_t* d_in, size_t container_size, const density_hip_header_t& h, uint8_t* d_out, size_t cap, uint8_t* ws,
-                        hipStream_t s, size_t ws_size, uint32_t* d_verdicts, unsigned flags, uint32_t* damaged_out) {
+                        hipStream_t s, size_t ws_size, uint32_t* d_verdicts, unsigned flags, uint32_t* damaged_out, const Recovery* rec) {
     if (const int rc = run_decode_container(c, d_in, container_size, h, d_out, cap, ws, s, nullptr, ws_size)) return rc;
     const DecodePlan p = plan_decode(h.algo, h.n_chunks, h.chunk_size);
     Profiler prof(c, s);
-    hipError_t e = launch_chunk_verdicts(reinterpret_cast<const uint32_t*>(p.produced(ws)), h.total_len, h.chunk_size, h.n_chunks, d_in + (h.container_len - header_trailer(h)),
-                                         d_verdicts, p.damaged(ws), p.err(ws), s);
+    uint32_t* d_acc = reinterpret_cast<uint32_t*>(p.produced(ws));
+    const uint8_t* d_trailer = d_in + (h.container_len - header_trailer(h));
+    hipError_t e = launch_chunk_verdicts(d_acc, h.total_len, h.chunk_size, h.n_chunks, d_trailer, d_verdicts, p.damaged(ws), p.err(ws), s);
     prof.mark("chunk_verdicts");
+    if (rec) {
+        // recovery: what the verdicts say can be rebuilt is rebuilt from the parity rows, summed again and held against the trailer once more
+        uint32_t* d_victims = p.victims(ws, h.n_chunks);
+        if (e == hipSuccess) e = launch_recover_rebuild(d_out, h.total_len, h.chunk_size, h.n_chunks, rec->d_rows, rec->n_groups, rec->row_bytes, d_verdicts, d_victims, d_acc, s);
+        prof.mark("recover_rebuild");
+        if (e == hipSuccess) e = launch_recover_verify(d_out, h.total_len, h.chunk_size, h.n_chunks, rec->n_groups, d_victims, d_acc, d_trailer, d_verdicts, p.damaged(ws), p.recovered(ws), s);
+        prof.mark("recover_verify");
+    }
     if (flags & DENSITY_HIP_SALVAGE_BLANK) {
         if (e == hipSuccess) e = launch_blank_chunks(d_out, h.total_len, h.chunk_size, h.n_chunks, d_verdicts, s);
         prof.mark("blank_chunks");
     }
     if (e != hipSuccess) { set_error("kernel launch (verdicts)", e); return DENSITY_HIP_ERR_RUNTIME; }
-    if (damaged_out) {
-        uint32_t h_err = 0, damaged = 0;
-        e = read_back(s, p.err(ws), &h_err, &damaged, p.damaged(ws), sizeof(damaged));
+    if (damaged_out || (rec && rec->recovered_out)) {
+        uint32_t h_err = 0, counts[2] = {0, 0};                                        // {damaged, recovered}: neighbours in the workspace
+        e = read_back(s, p.err(ws), &h_err, counts, p.damaged(ws), rec ? sizeof(counts) : sizeof(counts[0]));
         if (e != hipSuccess) { set_error("decode (device)", e); return DENSITY_HIP_ERR_RUNTIME; }
-        *damaged_out = damaged;
-        if (h_err) {
+        if (damaged_out) *damaged_out = counts[0];
+        if (rec && rec->recovered_out) *rec->recovered_out = counts[1];
+        if (h_err && !(rec && counts[0] == 0)) {                                       // (recovered whole: every chunk's content has been verified, whatever a decoder raised)
             const bool format = h_err & ~kErrChecksum;
             char msg[160];
-            std::snprintf(msg, sizeof(msg), "%s: %u of %u chunks damaged", format ? "malformed or truncated container payload" : "checksum mismatch", damaged, h.n_chunks);
+            int at = std::snprintf(msg, sizeof(msg), "%s: %u of %u chunks damaged", format ? "malformed or truncated container payload" : "checksum mismatch", counts[0], h.n_chunks);
+            if (rec) std::snprintf(msg + at, sizeof(msg) - at, ", %u recovered", counts[1]);
             set_error(msg);
             return format ? DENSITY_HIP_ERR_FORMAT : DENSITY_HIP_ERR_CHECKSUM;
         }
     }
+    return DENSITY_HIP_OK;
+}
+
+int check_parity_header(const density_hip_parity_header_t& ph, const density_hip_header_t& h, size_t parity_size) {
+    if (ph.magic != DENSITY_HIP_PARITY_MAGIC || ph.version != 1) { set_error("bad parity header"); return DENSITY_HIP_ERR_FORMAT; }
+    if (ph.chunk_size != h.chunk_size || ph.n_chunks != h.n_chunks || ph.total_len != h.total_len) { set_error("recover: the parity blob is not this container's (chunk size, chunks, length)"); return DENSITY_HIP_ERR_ARGUMENT; }
+    const density_hip_parity_header_t want = make_parity_header(h.total_len, h.chunk_size, ph.n_groups);
+    if ((h.n_chunks && !ph.n_groups) || ph.n_groups != want.n_groups || ph.row_bytes != want.row_bytes) { set_error("bad parity header (groups, row length)"); return DENSITY_HIP_ERR_FORMAT; }
+    if (parity_size < parity_bytes(ph)) { set_error("parity blob shorter than its header and rows"); return DENSITY_HIP_ERR_FORMAT; }
     return DENSITY_HIP_OK;
 }
 
@@ -611,6 +631,58 @@ int density_hip_decode_device_verdicts(const void* d_container, size_t container
     uint8_t* ws = nullptr;
     if (const int rc = resolve_workspace(c, d_workspace, workspace_size, dp.total, dp.total_with_passes, &ws, &workspace_size)) return rc;
     return run_decode_verdicts(c, (const uint8_t*)d_container, container_size, h, (uint8_t*)d_output, output_capacity, ws, s, workspace_size, d_verdicts, flags, damaged_out);
+}
+
+int density_hip_decode_device_recover(const void* d_container, size_t container_size, const density_hip_header_t* header, const void* d_parity, size_t parity_size,
+                                      const density_hip_parity_header_t* parity_header, void* d_output, size_t output_capacity, void* d_workspace, size_t workspace_size,
+                                      void* stream, uint32_t* d_verdicts, unsigned flags, uint32_t* damaged_out, uint32_t* recovered_out) {
+    g_last_error.clear();
+    if (!d_container || container_size < sizeof(density_hip_header_t) || (!d_output && output_capacity) || (flags & ~DENSITY_HIP_SALVAGE_BLANK) || (uintptr_t)d_verdicts % 4 != 0 || !d_parity) {
+        set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT;
+    }
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return DENSITY_HIP_ERR_RUNTIME;
+    std::lock_guard<std::mutex> lk(c->mu);
+    density_hip_header_t h;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (const int rc = container_header(header, d_container, container_size, s, &h)) return rc;
+    if (!(h.flags & DENSITY_HIP_FLAG_CHECKSUM)) { set_error("recover: the container is not sealed (no trailer to hold its chunks against)"); return DENSITY_HIP_ERR_ARGUMENT; }
+    if (!d_verdicts && h.n_chunks) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
+    if (parity_size < sizeof(density_hip_parity_header_t)) { set_error("parity blob shorter than its header"); return DENSITY_HIP_ERR_FORMAT; }
+    density_hip_parity_header_t ph;
+    if (parity_header) ph = *parity_header;
+    else {
+        hipError_t e = hipMemcpyAsync(&ph, d_parity, sizeof(ph), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { set_error("parity header read-back", e); return DENSITY_HIP_ERR_RUNTIME; }
+    }
+    if (const int rc = check_parity_header(ph, h, parity_size)) return rc;
+    const DecodePlan dp = plan_decode(h.algo, h.n_chunks, h.chunk_size);      // (the workspace rules of density_hip_decode_device)
+    uint8_t* ws = nullptr;
+    if (const int rc = resolve_workspace(c, d_workspace, workspace_size, dp.total, dp.total_with_passes, &ws, &workspace_size)) return rc;
+    const Recovery rec{(const uint8_t*)d_parity + sizeof(ph), ph.n_groups, ph.row_bytes, recovered_out};
+    return run_decode_verdicts(c, (const uint8_t*)d_container, container_size, h, (uint8_t*)d_output, output_capacity, ws, s, workspace_size, d_verdicts, flags, damaged_out, &rec);
+}
+
+size_t density_hip_parity_size(size_t input_size, size_t chunk_size, uint32_t n_groups) {
+    if (!valid_chunk(chunk_size) || chunk_count(input_size, chunk_size) > 0xffffffffull || (input_size && !n_groups)) return 0;
+    return parity_bytes(make_parity_header(input_size, chunk_size, n_groups));
+}
+
+int density_hip_parity_device(const void* d_input, size_t input_size, size_t chunk_size, uint32_t n_groups, void* d_parity, size_t parity_capacity, void* stream) {
+    g_last_error.clear();
+    const size_t need = density_hip_parity_size(input_size, chunk_size, n_groups);
+    if (!need || (!d_input && input_size) || !d_parity) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
+    if (parity_capacity < need) { set_error("parity capacity below density_hip_parity_size()"); return DENSITY_HIP_ERR_CAPACITY; }
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return DENSITY_HIP_ERR_RUNTIME;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    Profiler prof(c, s);
+    const hipError_t e = launch_parity_rows((const uint8_t*)d_input, make_parity_header(input_size, chunk_size, n_groups), (uint8_t*)d_parity, s);
+    prof.mark("parity_rows");
+    if (e != hipSuccess) { set_error("kernel launch (parity)", e); return DENSITY_HIP_ERR_RUNTIME; }
+    return DENSITY_HIP_OK;
 }
 
 int density_hip_checksum_device(const void* d_data, size_t size, size_t chunk_size, uint32_t* d_sums, void* stream) {

@@ -218,6 +218,51 @@ size_t encode_container_staged(DeviceCtx* c, int algo, const uint8_t* input, siz
 using namespace density;
 using namespace density::api;
 
+namespace {
+// The host-pointer verdict decode and, with `parity` (a blob of parity_size bytes), the recover decode: staged whole, like every sealed container.
+size_t decode_verdicts_staged(const uint8_t* container, size_t container_size, const uint8_t* parity, size_t parity_size, uint8_t* output, size_t output_size,
+                              uint32_t* verdicts, size_t verdict_capacity, unsigned flags, uint32_t* damaged_out, uint32_t* recovered_out) {
+    g_last_error.clear();
+    if (damaged_out) *damaged_out = 0;
+    if (!container || container_size < sizeof(density_hip_header_t) || (!output && output_size) || (flags & ~DENSITY_HIP_SALVAGE_BLANK)) { set_error("bad argument"); return 0; }
+    density_hip_header_t h;
+    std::memcpy(&h, container, sizeof(h));
+    if (check_header(h, container_size) != DENSITY_HIP_OK) { set_error("bad container header"); return 0; }
+    if (!(h.flags & DENSITY_HIP_FLAG_CHECKSUM)) { set_error("verdicts: the container is not sealed (no trailer to hold its chunks against)"); return 0; }
+    if (h.total_len > output_size) { set_error("output buffer too small"); return 0; }
+    if (h.n_chunks > verdict_capacity || (!verdicts && h.n_chunks)) { set_error("verdict buffer too small"); return 0; }
+    density_hip_parity_header_t ph{};
+    if (parity) {
+        if (parity_size < sizeof(ph)) { set_error("parity blob shorter than its header"); return 0; }
+        std::memcpy(&ph, parity, sizeof(ph));
+        if (check_parity_header(ph, h, parity_size) != DENSITY_HIP_OK) return 0;
+    }
+    if (h.total_len == 0) return 0;
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    // the verdict words lie behind the output in its staging buffer, the parity rows behind the container in its
+    const size_t verdicts_at = align_up(h.total_len, kAlign), rows_at = align_up(h.container_len, kAlign), rows_bytes = parity ? parity_bytes(ph) - sizeof(ph) : 0;
+    hipError_t e = ensure_staging(c, rows_at + rows_bytes, verdicts_at + 4 * (size_t)h.n_chunks, plan_decode(h.algo, h.n_chunks, h.chunk_size).total_with_passes);
+    if (e == hipSuccess) e = copy_host_side_pinned(c->stage_in.p, container, h.container_len, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && parity) e = copy_host_side_pinned((uint8_t*)c->stage_in.p + rows_at, parity + sizeof(ph), rows_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) { set_error("staging (H2D)", e); return 0; }
+    uint8_t* d_out = (uint8_t*)c->stage_out.p;
+    uint32_t damaged = h.n_chunks;                                                                   // (written wherever the verdicts are valid)
+    const Recovery rec{(const uint8_t*)c->stage_in.p + rows_at, ph.n_groups, ph.row_bytes, recovered_out};
+    const int rc = run_decode_verdicts(c, (const uint8_t*)c->stage_in.p, h.container_len, h, d_out, h.total_len, (uint8_t*)c->work.p, c->stream, c->work.cap,
+                                       reinterpret_cast<uint32_t*>(d_out + verdicts_at), flags, &damaged, parity ? &rec : nullptr);
+    if (rc != DENSITY_HIP_OK && rc != DENSITY_HIP_ERR_CHECKSUM && rc != DENSITY_HIP_ERR_FORMAT) return 0;   // (those three come with verdicts: the driver reports no format error before it has them)
+    const std::string said = g_last_error;
+    e = copy_host_side_pinned(verdicts, d_out + verdicts_at, 4 * (size_t)h.n_chunks, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && damaged < h.n_chunks) e = copy_host_side_pinned(output, d_out, h.total_len, hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) { set_error("staging (D2H)", e); return 0; }
+    g_last_error = said;
+    if (damaged_out) *damaged_out = damaged;
+    return damaged < h.n_chunks ? (size_t)h.total_len : 0;
+}
+}  // namespace
+
 extern "C" {
 
 size_t density_hip_encode(int algo, const uint8_t* input, size_t input_size, uint8_t* output, size_t output_size, size_t chunk_size) {
@@ -278,36 +323,33 @@ size_t density_hip_decode(const uint8_t* container, size_t container_size, uint8
 
 size_t density_hip_decode_verdicts(const uint8_t* container, size_t container_size, uint8_t* output, size_t output_size, uint32_t* verdicts, size_t verdict_capacity,
                                    unsigned flags, uint32_t* damaged_out) {
+    return decode_verdicts_staged(container, container_size, nullptr, 0, output, output_size, verdicts, verdict_capacity, flags, damaged_out, nullptr);
+}
+
+size_t density_hip_decode_recover(const uint8_t* container, size_t container_size, const uint8_t* parity, size_t parity_size, uint8_t* output, size_t output_size,
+                                  uint32_t* verdicts, size_t verdict_capacity, unsigned flags, uint32_t* damaged_out, uint32_t* recovered_out) {
     g_last_error.clear();
-    if (damaged_out) *damaged_out = 0;
-    if (!container || container_size < sizeof(density_hip_header_t) || (!output && output_size) || (flags & ~DENSITY_HIP_SALVAGE_BLANK)) { set_error("bad argument"); return 0; }
-    density_hip_header_t h;
-    std::memcpy(&h, container, sizeof(h));
-    if (check_header(h, container_size) != DENSITY_HIP_OK) { set_error("bad container header"); return 0; }
-    if (!(h.flags & DENSITY_HIP_FLAG_CHECKSUM)) { set_error("verdicts: the container is not sealed (no trailer to hold its chunks against)"); return 0; }
-    if (h.total_len > output_size) { set_error("output buffer too small"); return 0; }
-    if (h.n_chunks > verdict_capacity || (!verdicts && h.n_chunks)) { set_error("verdict buffer too small"); return 0; }
-    if (h.total_len == 0) return 0;
+    if (recovered_out) *recovered_out = 0;
+    if (!parity) { if (damaged_out) *damaged_out = 0; set_error("bad argument"); return 0; }
+    return decode_verdicts_staged(container, container_size, parity, parity_size, output, output_size, verdicts, verdict_capacity, flags, damaged_out, recovered_out);
+}
+
+size_t density_hip_parity(const uint8_t* input, size_t input_size, size_t chunk_size, uint32_t n_groups, uint8_t* parity, size_t parity_capacity) {
+    g_last_error.clear();
+    const size_t need = density_hip_parity_size(input_size, chunk_size, n_groups);
+    if (!need || (!input && input_size) || !parity) { set_error("bad argument"); return 0; }
+    if (parity_capacity < need) { set_error("parity capacity below density_hip_parity_size()"); return 0; }
     DeviceCtx* c = acquire_ctx();
     if (!c) return 0;
     std::lock_guard<std::mutex> lk(c->mu);
-    // staged whole, like every sealed container; the verdict words lie behind the output in its staging buffer
-    const size_t verdicts_at = align_up(h.total_len, kAlign);
-    hipError_t e = ensure_staging(c, h.container_len, verdicts_at + 4 * (size_t)h.n_chunks, plan_decode(h.algo, h.n_chunks, h.chunk_size).total_with_passes);
-    if (e == hipSuccess) e = copy_host_side_pinned(c->stage_in.p, container, h.container_len, hipMemcpyHostToDevice, c->stream);
+    hipError_t e = ensure_staging(c, input_size, need, 0);
+    if (e == hipSuccess) e = copy_host_side_pinned(c->stage_in.p, input, input_size, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) { set_error("staging (H2D)", e); return 0; }
-    uint8_t* d_out = (uint8_t*)c->stage_out.p;
-    uint32_t damaged = h.n_chunks;                                                                   // (written wherever the verdicts are valid)
-    const int rc = run_decode_verdicts(c, (const uint8_t*)c->stage_in.p, h.container_len, h, d_out, h.total_len, (uint8_t*)c->work.p, c->stream, c->work.cap,
-                                       reinterpret_cast<uint32_t*>(d_out + verdicts_at), flags, &damaged);
-    if (rc != DENSITY_HIP_OK && rc != DENSITY_HIP_ERR_CHECKSUM && rc != DENSITY_HIP_ERR_FORMAT) return 0;   // (those three come with verdicts: the driver reports no format error before it has them)
-    const std::string said = g_last_error;
-    e = copy_host_side_pinned(verdicts, d_out + verdicts_at, 4 * (size_t)h.n_chunks, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && damaged < h.n_chunks) e = copy_host_side_pinned(output, d_out, h.total_len, hipMemcpyDeviceToHost, c->stream);
+    e = launch_parity_rows((const uint8_t*)c->stage_in.p, make_parity_header(input_size, chunk_size, n_groups), (uint8_t*)c->stage_out.p, c->stream);
+    if (e != hipSuccess) { set_error("kernel launch (parity)", e); return 0; }
+    e = copy_host_side_pinned(parity, c->stage_out.p, need, hipMemcpyDeviceToHost, c->stream);
     if (e != hipSuccess) { set_error("staging (D2H)", e); return 0; }
-    g_last_error = said;
-    if (damaged_out) *damaged_out = damaged;
-    return damaged < h.n_chunks ? (size_t)h.total_len : 0;
+    return need;
 }
 
 }  // extern "C"

@@ -4,42 +4,24 @@
 //
 // The sum kernel only reads: a chunk is cut into tiles of 32 KiB, a work-group takes tiles in a grid-stride loop, every lane has eight 16-byte loads
 // in flight, mixes each word with its index IN THE CHUNK (not its address: the buffer may start anywhere), and the work-group adds its partial sum
-// to the chunk's accumulator with one global atomic.  The sum commutes, so neither the tiles nor the atomics need an order.  A second, tiny kernel
-// turns the accumulators into C = fmix32(S + L), or compares them with a trailer.
+// to the chunk's accumulator with one global atomic (the tile: checksum_dev.hpp, shared with parity.hip).  The sum commutes, so neither the tiles nor
+// the atomics need an order.  A second, tiny kernel turns the accumulators into C = fmix32(S + L), or compares them with a trailer.
 //
 // Verdicts (density_hip_decode_device_verdicts): the accumulators a verifying decode leaves behind are held against the trailer once more, this time with
 // one word per chunk as the answer, and a fill kernel puts zeros where a damaged chunk's bytes stand.
-#include "checksum.hpp"
-#include "common.hpp"
+#include "checksum_dev.hpp"
 #include "kernels.hpp"
 
 namespace density {
 
 namespace {
 
-constexpr uint32_t kSumThreads = 256, kSumLoads = 8;
-constexpr uint32_t kSumTile = kSumThreads * 16u * kSumLoads;   // 32 KiB per work-group and trip
 constexpr uint32_t kSumMaxGroups = 256u * 8u;                  // eight work-groups a CU; what is left is taken in the grid-stride loop
 constexpr uint32_t kSmallThreads = 1024;
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint64_t align16(uint64_t v) { return (v + 15ull) & ~15ull; }
 __device__ __forceinline__ uint64_t ld64u(const uint8_t* p) { return *reinterpret_cast<const u64_u*>(p); }
 __device__ __forceinline__ void st64u(uint8_t* p, uint64_t v) { *reinterpret_cast<u64_u*>(p) = v; }
-
-// 16 bytes from any address: one global_load_dwordx4 (gfx950 global memory takes unaligned accesses, as for the dwords of common.hpp)
-__device__ __forceinline__ u32x4 load16(const uint8_t* p) {
-    u32x4 v;
-    __builtin_memcpy(&v, p, 16);
-    return v;
-}
-
-// bytes of chunk `c` of a buffer of `size` bytes cut every `chunk` bytes
-__device__ __forceinline__ uint32_t chunk_len(uint64_t size, uint32_t chunk, uint32_t c) {
-    const uint64_t begin = (uint64_t)c * chunk;
-    return size - begin < chunk ? (uint32_t)(size - begin) : chunk;
-}
 
 // d_geom (nullable; the asynchronous seal, whose geometry only the device knows): {chunk size, chunks} as seal_prepare_kernel took them from the
 // container's header, {.., 0} where that header is not to be followed
@@ -55,34 +37,7 @@ __global__ __launch_bounds__(kSumThreads) void checksum_tiles_kernel(const uint8
         const uint32_t len = chunk_len(size, chunk, c);
         if (t0 >= len) continue;                                             // (the ragged last chunk: the same for the whole work-group)
         const uint8_t* p = data + (uint64_t)c * chunk;
-        u32x4 v[kSumLoads];
-#pragma unroll
-        for (uint32_t j = 0; j < kSumLoads; ++j) {
-            const uint32_t off = t0 + (j * kSumThreads + threadIdx.x) * 16u;
-            v[j] = (off < len && len - off >= 16u) ? load16(p + off) : u32x4{0u, 0u, 0u, 0u};
-        }
-        uint32_t sum = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kSumLoads; ++j) {
-            const uint32_t off = t0 + (j * kSumThreads + threadIdx.x) * 16u, i = off / 4u;
-            if (off >= len) continue;
-            if (len - off >= 16u) {
-                sum += sum_term(v[j].x, i) + sum_term(v[j].y, i + 1u) + sum_term(v[j].z, i + 2u) + sum_term(v[j].w, i + 3u);
-            } else {                                                         // the chunk's last 1..15 bytes: whole words, then one padded with zeros
-                const uint32_t rem = len - off;
-                for (uint32_t k = 0; k < rem; k += 4u) {
-                    uint32_t w = 0;
-                    for (uint32_t b = 0; b < 4u && k + b < rem; ++b) w |= (uint32_t)p[off + k + b] << (8u * b);
-                    sum += sum_term(w, i + k / 4u);
-                }
-            }
-        }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
-        if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = sum;
-        __syncthreads();
-        if (threadIdx.x == 0) atomicAdd(acc + c, part[0] + part[1] + part[2] + part[3]);
-        __syncthreads();                                                     // (part is written again in the next trip)
+        sum_tile(p, len, t0, part, acc + c);
     }
 }
 
@@ -108,9 +63,10 @@ __global__ __launch_bounds__(256) void checksum_verdict_kernel(const uint32_t* _
     if (damaged) { atomicAdd(count, 1u); atomicOr(err, kErrChecksum); }
 }
 
-// Zeros over the output region of every chunk whose verdict is not 0 (the last chunk at its true length, `out` at any alignment): a chunk is cut into
-// tiles of 16 KiB, a work-group takes tiles in a grid-stride loop and leaves a tile of an intact chunk at its first load — the verdict word.  Inside a
-// tile: bytes up to the first 16-byte boundary of the ADDRESS, 16-byte stores, bytes behind the last whole one.
+// Zeros over the output region of every chunk whose verdict is DENSITY_HIP_CHUNK_DAMAGED — a chunk that parity.hip has rebuilt is kept — (the last chunk at its
+// true length, `out` at any alignment): a chunk is cut into tiles of 16 KiB, a work-group takes tiles in a grid-stride loop and leaves a tile of an intact
+// chunk at its first load — the verdict word.  Inside a tile: bytes up to the first 16-byte boundary of the ADDRESS, 16-byte stores, bytes behind the last
+// whole one.
 constexpr uint32_t kBlankThreads = 256, kBlankStores = 4;
 constexpr uint32_t kBlankTile = kBlankThreads * 16u * kBlankStores;   // 16 KiB per work-group and trip
 constexpr uint32_t kBlankMaxGroups = 256u * 32u;
@@ -120,7 +76,7 @@ __global__ __launch_bounds__(kBlankThreads) void blank_chunks_kernel(uint8_t* __
     const uint64_t units = (uint64_t)n_chunks * tiles;
     for (uint64_t u = blockIdx.x; u < units; u += gridDim.x) {
         const uint32_t c = (uint32_t)(u / tiles), t0 = (uint32_t)(u % tiles) * kBlankTile;
-        if (verdict[c] == 0u) continue;
+        if (verdict[c] != DENSITY_HIP_CHUNK_DAMAGED) continue;
         const uint32_t len = chunk_len(size, chunk, c);
         if (t0 >= len) continue;                                             // (the ragged last chunk)
         const uint32_t n = len - t0 < kBlankTile ? len - t0 : kBlankTile;

@@ -193,7 +193,7 @@ hipError_t launch_checksum(const uint8_t* d_data, uint64_t size, uint32_t chunk,
 // d_verdicts[c] = DENSITY_HIP_CHUNK_DAMAGED or 0 (4-byte aligned), *d_count (cleared here) the number of damaged chunks, kErrChecksum into *d_err.
 hipError_t launch_chunk_verdicts(const uint32_t* d_acc, uint64_t size, uint32_t chunk, uint32_t n_chunks, const uint8_t* d_expect, uint32_t* d_verdicts,
                                  uint32_t* d_count, uint32_t* d_err, hipStream_t stream);
-// zeros over chunk c's bytes of d_out (any alignment; the last chunk at its true length) for every c with d_verdicts[c] != 0
+// zeros over chunk c's bytes of d_out (any alignment; the last chunk at its true length) for every c with d_verdicts[c] == DENSITY_HIP_CHUNK_DAMAGED
 hipError_t launch_blank_chunks(uint8_t* d_out, uint64_t size, uint32_t chunk, uint32_t n_chunks, const uint32_t* d_verdicts, hipStream_t stream);
 // Seals the container an encoder has just written for d_in, in place, from its header ON THE DEVICE: trailer, flag, new container_len.  d_geom: 4
 // words, d_acc: a word per chunk (at most one per 256 bytes of input) of scratch.  *d_err bit 1: not this input's unsealed container; bit 2: the capacity
@@ -202,5 +202,17 @@ hipError_t launch_seal(const uint8_t* d_in, uint64_t input_size, uint8_t* d_cont
                        hipStream_t stream);
 // a trailer of n_chunks words to its place behind the packed container the layout kernel has just written (density_hip_pack_device)
 hipError_t launch_move_trailer(const uint8_t* d_trailer, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err, hipStream_t stream);
+
+// ---- parity.hip (recovery records: the parity blob "DHP1" of include/density_hip.h, and the rebuild behind a verdict decode) ----
+// The blob of d_data (hdr.total_len bytes, any alignment) into d_blob (any alignment): hdr itself, then hdr.n_groups rows of hdr.row_bytes bytes.
+hipError_t launch_parity_rows(const uint8_t* d_data, const density_hip_parity_header_t& hdr, uint8_t* d_blob, hipStream_t stream);
+// Behind launch_chunk_verdicts.  d_victim[g] (n_groups words of scratch) = the only chunk of group g with verdict DENSITY_HIP_CHUNK_DAMAGED, if there is exactly
+// one: its bytes in d_out become row g of d_rows (n_groups rows of row_bytes bytes, any alignment) XOR the other members' bytes, and d_acc[victim] = 0.
+hipError_t launch_recover_rebuild(uint8_t* d_out, uint64_t size, uint32_t chunk, uint32_t n_chunks, const uint8_t* d_rows, uint32_t n_groups, uint32_t row_bytes,
+                                  const uint32_t* d_verdicts, uint32_t* d_victim, uint32_t* d_acc, hipStream_t stream);
+// ... then the victims summed again into d_acc and held against the trailer d_expect: DENSITY_HIP_CHUNK_RECOVERED into d_verdicts where it matches now, one less in
+// *d_damaged and one more in *d_recovered (cleared here) for each.
+hipError_t launch_recover_verify(const uint8_t* d_out, uint64_t size, uint32_t chunk, uint32_t n_chunks, uint32_t n_groups, const uint32_t* d_victim, uint32_t* d_acc,
+                                 const uint8_t* d_expect, uint32_t* d_verdicts, uint32_t* d_damaged, uint32_t* d_recovered, hipStream_t stream);
 
 }  // namespace density

@@ -288,6 +288,63 @@ int density_hip_decode_device_verdicts(const void* d_container, size_t container
 size_t density_hip_decode_verdicts(const uint8_t* container, size_t container_size, uint8_t* output, size_t output_size, uint32_t* verdicts,
                                    size_t verdict_capacity, unsigned flags, uint32_t* damaged_out);
 
+/* Recovery records: the parity blob "DHP1" and the decode that rebuilds damaged chunks from it.
+ * The blob is a SIDECAR: it is not part of any container, no container flag announces it, and every call above behaves as it does without one.  It holds
+ * n_groups XOR rows over the INPUT's chunks, interleaved so that adjacent chunks lie in different groups.  Layout (little-endian):
+ *     [0,32)                          density_hip_parity_header_t
+ *     [32, 32 + n_groups * row_bytes)  row 0, row 1, ...
+ * row_bytes = round_up(min(chunk_size, total_len), 16); n_groups = min(requested, n_chunks); row g = XOR of the input chunks i with i % n_groups == g, each
+ * zero-padded to row_bytes.  The blob depends on the input, chunk_size and n_groups alone — not on the algorithm, not on the container's form — so one blob
+ * serves the packed, slotted and paged containers of all three algorithms made from that input with that chunk size.  An input of zero bytes gives a bare
+ * header with n_groups 0.  The rows carry no checksum of their own: a rebuilt chunk is accepted only against the container's trailer, so a damaged row
+ * cannot pass wrong bytes.  A chunk can be rebuilt as long as it is the only damaged chunk of its group: with G groups any burst of up to G neighbouring
+ * chunks is recovered whole.  (A CPU reader rebuilds chunk k the same way: INTEGRATION.md.)
+ *   density_hip_parity_size: the exact blob size; 0 for an invalid chunk_size — 0 included: pass the chunk size the container has, from its header or from
+ *     density_hip_auto_chunk_for() — or for n_groups == 0 with a non-empty input.  Pure host arithmetic.
+ *   density_hip_parity_device: the blob of a device buffer, asynchronous on `stream`; d_input and d_parity at any byte alignment.  A parity_capacity below
+ *     density_hip_parity_size() is DENSITY_HIP_ERR_CAPACITY at once, nothing written.  Profiling mark: "parity_rows".
+ *   density_hip_parity: the same on host pointers, staged whole; returns the bytes written, 0 on failure. */
+#define DENSITY_HIP_PARITY_MAGIC 0x31504844u /* "DHP1" */
+typedef struct density_hip_parity_header {
+    uint32_t magic;          /* DENSITY_HIP_PARITY_MAGIC */
+    uint8_t  version;        /* 1 */
+    uint8_t  reserved0;      /* 0 */
+    uint16_t reserved1;      /* 0 */
+    uint32_t chunk_size;     /* of the input's cut, and of every container the blob serves */
+    uint32_t n_chunks;       /* ceil(total_len / chunk_size) */
+    uint64_t total_len;      /* bytes of input */
+    uint32_t n_groups;       /* rows in the blob: 1 .. n_chunks (0 for an empty input) */
+    uint32_t row_bytes;      /* round_up(min(chunk_size, total_len), 16) */
+} density_hip_parity_header_t;
+size_t density_hip_parity_size(size_t input_size, size_t chunk_size, uint32_t n_groups);
+int density_hip_parity_device(const void* d_input, size_t input_size, size_t chunk_size, uint32_t n_groups, void* d_parity, size_t parity_capacity, void* stream);
+size_t density_hip_parity(const uint8_t* input, size_t input_size, size_t chunk_size, uint32_t n_groups, uint8_t* parity, size_t parity_capacity);
+/* density_hip_decode_device_recover runs density_hip_decode_device_verdicts unchanged (the same kernels, the same workspace rules and sizes) and then, with the blob:
+ *   - rebuild: for every group with exactly ONE damaged member k, chunk k's region of d_output is replaced by row g XOR the regions of the group's other
+ *     members (the last chunk at its true length; no byte past total_len is written);
+ *   - re-verify: chunk k is summed again and held against trailer entry k: a match makes its verdict DENSITY_HIP_CHUNK_RECOVERED, anything else (a damaged
+ *     row, a damaged trailer entry) leaves it DENSITY_HIP_CHUNK_DAMAGED;
+ *   - groups with two or more damaged members are left alone; DENSITY_HIP_SALVAGE_BLANK then zeroes whatever is STILL damaged.
+ * So a verdict is not DENSITY_HIP_CHUNK_DAMAGED if and only if the region's bytes have the trailer's checksum.  *damaged_out = chunks still damaged,
+ * *recovered_out = chunks rebuilt (both HOST, each optional; with either the call synchronises `stream`, with both NULL it is fully asynchronous and leaves the
+ * two counts in the second and third 32-bit word of d_workspace where the caller passed one).  Returns DENSITY_HIP_OK when no chunk remains damaged — also where
+ * a decoder raised a format error on the way: every chunk's content has been verified —, otherwise DENSITY_HIP_ERR_FORMAT if a decoder raised one, otherwise
+ * DENSITY_HIP_ERR_CHECKSUM.
+ *   - d_parity / parity_size: the blob on the device, at any byte alignment; parity_header: optional HOST copy of its first 32 bytes (NULL: read back, one
+ *     small synchronous copy).
+ *   - DENSITY_HIP_ERR_ARGUMENT, nothing written: an unsealed container, unknown bits in `flags`, a parity header whose chunk_size / n_chunks / total_len are not
+ *     the container's.  DENSITY_HIP_ERR_FORMAT, nothing written: a wrong magic or version, n_groups outside 1 .. n_chunks, a row_bytes that is not the
+ *     formula's, a parity_size short of header plus rows.
+ * density_hip_decode_recover is the host-pointer form, shaped like density_hip_decode_verdicts: it returns total_len if at least one chunk is not damaged and no
+ * argument or capacity error occurred, else 0.
+ * Profiling marks: those of density_hip_decode_device_verdicts up to "chunk_verdicts", then "recover_rebuild", "recover_verify" and, when blanking runs, "blank_chunks". */
+#define DENSITY_HIP_CHUNK_RECOVERED 2u
+int density_hip_decode_device_recover(const void* d_container, size_t container_size, const density_hip_header_t* header, const void* d_parity, size_t parity_size,
+                                      const density_hip_parity_header_t* parity_header, void* d_output, size_t output_capacity, void* d_workspace,
+                                      size_t workspace_size, void* stream, uint32_t* d_verdicts, unsigned flags, uint32_t* damaged_out, uint32_t* recovered_out);
+size_t density_hip_decode_recover(const uint8_t* container, size_t container_size, const uint8_t* parity, size_t parity_size, uint8_t* output, size_t output_size,
+                                  uint32_t* verdicts, size_t verdict_capacity, unsigned flags, uint32_t* damaged_out, uint32_t* recovered_out);
+
 /* Device-resident single reference stream (the format of section 1, device pointers).  `size_out` is a HOST
  * pointer and must be non-NULL: the call synchronises `stream`. */
 int density_hip_stream_encode_device(int algo, const void* d_input, size_t input_size, void* d_output,
