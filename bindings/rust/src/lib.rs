@@ -55,6 +55,11 @@ pub mod sealed {
         pub fn density_hip_parity_device(d_input: *const core::ffi::c_void, input_size: usize, chunk_size: usize, n_groups: u32, d_parity: *mut core::ffi::c_void,
                                          parity_capacity: usize, stream: *mut core::ffi::c_void) -> i32;
         pub fn density_hip_parity(input: *const u8, input_size: usize, chunk_size: usize, n_groups: u32, parity: *mut u8, parity_capacity: usize) -> usize;
+        /// version 2 of the blob: Q rows over GF(2^8) behind the P rows, so that any two damaged chunks of a group (of at most 255) are rebuilt
+        pub fn density_hip_parity2_size(input_size: usize, chunk_size: usize, n_groups: u32) -> usize;
+        pub fn density_hip_parity2_device(d_input: *const core::ffi::c_void, input_size: usize, chunk_size: usize, n_groups: u32, d_parity: *mut core::ffi::c_void,
+                                          parity_capacity: usize, stream: *mut core::ffi::c_void) -> i32;
+        pub fn density_hip_parity2(input: *const u8, input_size: usize, chunk_size: usize, n_groups: u32, parity: *mut u8, parity_capacity: usize) -> usize;
         pub fn density_hip_decode_device_recover(d_container: *const core::ffi::c_void, container_size: usize, header: *const DensityHipHeader, d_parity: *const core::ffi::c_void,
                                                  parity_size: usize, parity_header: *const DensityHipParityHeader, d_output: *mut core::ffi::c_void, output_capacity: usize,
                                                  d_workspace: *mut core::ffi::c_void, workspace_size: usize, stream: *mut core::ffi::c_void, d_verdicts: *mut u32,

@@ -313,12 +313,12 @@ def parity_size(input_size, chunk_size, n_groups):
 
 
 def parse_parity_header(raw32):
-    """The header of a host-resident parity blob; raises DecodeError where it is not one."""
+    """The header of a host-resident parity blob of version 1 or 2; raises DecodeError where it is not one."""
     raw = bytes(raw32[:32])
     if len(raw) < 32:
         raise DecodeError("parity blob shorter than its header")
     h = _lib.ParityHeader.from_buffer_copy(raw)
-    if h.magic != _lib.PARITY_MAGIC or h.version != 1:
+    if h.magic != _lib.PARITY_MAGIC or h.version not in (1, 2):
         raise DecodeError("not a parity blob (magic, version)")
     return h
 
@@ -338,10 +338,31 @@ def parity(input, chunk_size, n_groups, output):
     return r
 
 
+def parity2_size(input_size, chunk_size, n_groups):
+    """parity_size for version 2 of the blob (n_groups P rows, then as many Q rows over GF(2^8): any two chunks of a group can be rebuilt); 0 also where a
+    group would have more than 255 chunks."""
+    return int(_lib.lib().density_hip_parity2_size(input_size, chunk_size, n_groups))
+
+
+def parity2_device(d_in, n, chunk_size, n_groups, d_parity, cap, stream=0):
+    """parity_device for version 2 of the blob (cap >= parity2_size())."""
+    _check(_lib.lib().density_hip_parity2_device(d_in, n, chunk_size, n_groups, d_parity, cap, stream), EncodeError)
+
+
+def parity2(input, chunk_size, n_groups, output):
+    """parity for version 2 of the blob; returns the bytes written."""
+    ia, n, k1 = _ro(input)
+    oa, cap, k2 = _rw(output)
+    r = _lib.lib().density_hip_parity2(ia, n, chunk_size, n_groups, oa, cap)
+    if r == 0:
+        raise EncodeError(_lib.last_error())
+    return r
+
+
 def decode_device_recover(d_container, container_size, d_parity, parity_size, d_out, cap, d_verdicts, header=None, parity_header=None, stream=0, workspace=(0, 0),
                           blank=True, sync=True):
-    """decode_device_verdicts, then every chunk that is the only damaged one of its parity group rebuilt from the blob at d_parity and verified again: its
-    verdict becomes _lib.CHUNK_RECOVERED.  Returns (return code, chunks still damaged, chunks recovered) — OK wherever nothing remains damaged, else
+    """decode_device_verdicts, then every chunk that is the only damaged one of its parity group — with a version-2 blob (parity2_device): one of the only two —
+    rebuilt from the blob at d_parity and verified again: its verdict becomes _lib.CHUNK_RECOVERED.  Returns (return code, chunks still damaged, chunks recovered) — OK wherever nothing remains damaged, else
     ERR_FORMAT or ERR_CHECKSUM, each with valid verdicts — or None with sync=False.  Anything else (an unsealed container, a blob that is not this
     container's or is malformed, a capacity) raises DecodeError."""
     damaged, recovered = ctypes.c_uint32(0), ctypes.c_uint32(0)
@@ -355,7 +376,7 @@ def decode_device_recover(d_container, container_size, d_parity, parity_size, d_
 
 
 def decode_recover(container, parity, output, blank=True):
-    """decode_verdicts with a parity blob: returns (bytes written, indices of the chunks still damaged, indices of the chunks recovered).  Raises ChecksumError
+    """decode_verdicts with a parity blob of either version (parity, parity2): returns (bytes written, indices of the chunks still damaged, indices of the chunks recovered).  Raises ChecksumError
     (damaged_chunks: all of them) where every chunk remains damaged, DecodeError for anything that is not damage."""
     ia, n, k1 = _ro(container)
     pa, pn, k3 = _ro(parity)

@@ -331,9 +331,9 @@ int run_decode_verdicts(DeviceCtx* c, const uint8_t* d_in, size_t container_size
     if (rec) {
         // recovery: what the verdicts say can be rebuilt is rebuilt from the parity rows, summed again and held against the trailer once more
         uint32_t* d_victims = p.victims(ws, h.n_chunks);
-        if (e == hipSuccess) e = launch_recover_rebuild(d_out, h.total_len, h.chunk_size, h.n_chunks, rec->d_rows, rec->n_groups, rec->row_bytes, d_verdicts, d_victims, d_acc, s);
+        if (e == hipSuccess) e = launch_recover_rebuild(d_out, h.total_len, h.chunk_size, h.n_chunks, rec->d_rows, rec->n_groups, rec->row_bytes, rec->with_q, d_verdicts, d_victims, d_acc, s);
         prof.mark("recover_rebuild");
-        if (e == hipSuccess) e = launch_recover_verify(d_out, h.total_len, h.chunk_size, h.n_chunks, rec->n_groups, d_victims, d_acc, d_trailer, d_verdicts, p.damaged(ws), p.recovered(ws), s);
+        if (e == hipSuccess) e = launch_recover_verify(d_out, h.total_len, h.chunk_size, h.n_chunks, rec->n_groups, rec->with_q, d_victims, d_acc, d_trailer, d_verdicts, p.damaged(ws), p.recovered(ws), s);
         prof.mark("recover_verify");
     }
     if (flags & DENSITY_HIP_SALVAGE_BLANK) {
@@ -360,12 +360,19 @@ int run_decode_verdicts(DeviceCtx* c, const uint8_t* d_in, size_t container_size
 }
 
 int check_parity_header(const density_hip_parity_header_t& ph, const density_hip_header_t& h, size_t parity_size) {
-    if (ph.magic != DENSITY_HIP_PARITY_MAGIC || ph.version != 1) { set_error("bad parity header"); return DENSITY_HIP_ERR_FORMAT; }
+    if (ph.magic != DENSITY_HIP_PARITY_MAGIC || (ph.version != 1 && ph.version != 2)) { set_error("bad parity header"); return DENSITY_HIP_ERR_FORMAT; }
     if (ph.chunk_size != h.chunk_size || ph.n_chunks != h.n_chunks || ph.total_len != h.total_len) { set_error("recover: the parity blob is not this container's (chunk size, chunks, length)"); return DENSITY_HIP_ERR_ARGUMENT; }
     const density_hip_parity_header_t want = make_parity_header(h.total_len, h.chunk_size, ph.n_groups);
     if ((h.n_chunks && !ph.n_groups) || ph.n_groups != want.n_groups || ph.row_bytes != want.row_bytes) { set_error("bad parity header (groups, row length)"); return DENSITY_HIP_ERR_FORMAT; }
+    if (ph.version == 2 && parity_group_members(ph) > kParityQMembers) { set_error("bad parity header (version 2: a group of more than 255 chunks)"); return DENSITY_HIP_ERR_FORMAT; }
     if (parity_size < parity_bytes(ph)) { set_error("parity blob shorter than its header and rows"); return DENSITY_HIP_ERR_FORMAT; }
     return DENSITY_HIP_OK;
+}
+
+size_t parity_size_of(uint8_t version, size_t input_size, size_t chunk_size, uint32_t n_groups) {
+    if (!valid_chunk(chunk_size) || chunk_count(input_size, chunk_size) > 0xffffffffull || (input_size && !n_groups)) return 0;
+    const density_hip_parity_header_t ph = make_parity_header(input_size, chunk_size, n_groups, version);
+    return version == 2 && parity_group_members(ph) > kParityQMembers ? 0 : parity_bytes(ph);
 }
 
 // slotted container -> packed container (the wire form): header, size table and block index are copied, the payloads gathered
@@ -507,6 +514,22 @@ int container_header(const density_hip_header_t* header, const void* d_container
         if (e != hipSuccess) { set_error("header read-back", e); return DENSITY_HIP_ERR_RUNTIME; }
     }
     if (check_header(*h, container_size) != DENSITY_HIP_OK) { set_error("bad container header"); return DENSITY_HIP_ERR_FORMAT; }
+    return DENSITY_HIP_OK;
+}
+// density_hip_parity_device and density_hip_parity2_device: they differ in the blob's version
+int parity_device(uint8_t version, const void* d_input, size_t input_size, size_t chunk_size, uint32_t n_groups, void* d_parity, size_t parity_capacity, void* stream) {
+    g_last_error.clear();
+    const size_t need = parity_size_of(version, input_size, chunk_size, n_groups);
+    if (!need || (!d_input && input_size) || !d_parity) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
+    if (parity_capacity < need) { set_error("parity capacity below density_hip_parity_size() / density_hip_parity2_size()"); return DENSITY_HIP_ERR_CAPACITY; }
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return DENSITY_HIP_ERR_RUNTIME;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    Profiler prof(c, s);
+    const hipError_t e = launch_parity_rows((const uint8_t*)d_input, make_parity_header(input_size, chunk_size, n_groups, version), (uint8_t*)d_parity, s);
+    prof.mark(version == 2 ? "parity2_rows" : "parity_rows");
+    if (e != hipSuccess) { set_error("kernel launch (parity)", e); return DENSITY_HIP_ERR_RUNTIME; }
     return DENSITY_HIP_OK;
 }
 }  // namespace
@@ -660,29 +683,18 @@ int density_hip_decode_device_recover(const void* d_container, size_t container_
     const DecodePlan dp = plan_decode(h.algo, h.n_chunks, h.chunk_size);      // (the workspace rules of density_hip_decode_device)
     uint8_t* ws = nullptr;
     if (const int rc = resolve_workspace(c, d_workspace, workspace_size, dp.total, dp.total_with_passes, &ws, &workspace_size)) return rc;
-    const Recovery rec{(const uint8_t*)d_parity + sizeof(ph), ph.n_groups, ph.row_bytes, recovered_out};
+    const Recovery rec{(const uint8_t*)d_parity + sizeof(ph), ph.n_groups, ph.row_bytes, ph.version == 2, recovered_out};
     return run_decode_verdicts(c, (const uint8_t*)d_container, container_size, h, (uint8_t*)d_output, output_capacity, ws, s, workspace_size, d_verdicts, flags, damaged_out, &rec);
 }
 
-size_t density_hip_parity_size(size_t input_size, size_t chunk_size, uint32_t n_groups) {
-    if (!valid_chunk(chunk_size) || chunk_count(input_size, chunk_size) > 0xffffffffull || (input_size && !n_groups)) return 0;
-    return parity_bytes(make_parity_header(input_size, chunk_size, n_groups));
-}
+size_t density_hip_parity_size(size_t input_size, size_t chunk_size, uint32_t n_groups) { return parity_size_of(1, input_size, chunk_size, n_groups); }
+size_t density_hip_parity2_size(size_t input_size, size_t chunk_size, uint32_t n_groups) { return parity_size_of(2, input_size, chunk_size, n_groups); }
 
 int density_hip_parity_device(const void* d_input, size_t input_size, size_t chunk_size, uint32_t n_groups, void* d_parity, size_t parity_capacity, void* stream) {
-    g_last_error.clear();
-    const size_t need = density_hip_parity_size(input_size, chunk_size, n_groups);
-    if (!need || (!d_input && input_size) || !d_parity) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
-    if (parity_capacity < need) { set_error("parity capacity below density_hip_parity_size()"); return DENSITY_HIP_ERR_CAPACITY; }
-    DeviceCtx* c = acquire_ctx();
-    if (!c) return DENSITY_HIP_ERR_RUNTIME;
-    std::lock_guard<std::mutex> lk(c->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    Profiler prof(c, s);
-    const hipError_t e = launch_parity_rows((const uint8_t*)d_input, make_parity_header(input_size, chunk_size, n_groups), (uint8_t*)d_parity, s);
-    prof.mark("parity_rows");
-    if (e != hipSuccess) { set_error("kernel launch (parity)", e); return DENSITY_HIP_ERR_RUNTIME; }
-    return DENSITY_HIP_OK;
+    return parity_device(1, d_input, input_size, chunk_size, n_groups, d_parity, parity_capacity, stream);
+}
+int density_hip_parity2_device(const void* d_input, size_t input_size, size_t chunk_size, uint32_t n_groups, void* d_parity, size_t parity_capacity, void* stream) {
+    return parity_device(2, d_input, input_size, chunk_size, n_groups, d_parity, parity_capacity, stream);
 }
 
 int density_hip_checksum_device(const void* d_data, size_t size, size_t chunk_size, uint32_t* d_sums, void* stream) {

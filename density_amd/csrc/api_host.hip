@@ -249,7 +249,7 @@ size_t decode_verdicts_staged(const uint8_t* container, size_t container_size, c
     if (e != hipSuccess) { set_error("staging (H2D)", e); return 0; }
     uint8_t* d_out = (uint8_t*)c->stage_out.p;
     uint32_t damaged = h.n_chunks;                                                                   // (written wherever the verdicts are valid)
-    const Recovery rec{(const uint8_t*)c->stage_in.p + rows_at, ph.n_groups, ph.row_bytes, recovered_out};
+    const Recovery rec{(const uint8_t*)c->stage_in.p + rows_at, ph.n_groups, ph.row_bytes, ph.version == 2, recovered_out};
     const int rc = run_decode_verdicts(c, (const uint8_t*)c->stage_in.p, h.container_len, h, d_out, h.total_len, (uint8_t*)c->work.p, c->stream, c->work.cap,
                                        reinterpret_cast<uint32_t*>(d_out + verdicts_at), flags, &damaged, parity ? &rec : nullptr);
     if (rc != DENSITY_HIP_OK && rc != DENSITY_HIP_ERR_CHECKSUM && rc != DENSITY_HIP_ERR_FORMAT) return 0;   // (those three come with verdicts: the driver reports no format error before it has them)
@@ -260,6 +260,25 @@ size_t decode_verdicts_staged(const uint8_t* container, size_t container_size, c
     g_last_error = said;
     if (damaged_out) *damaged_out = damaged;
     return damaged < h.n_chunks ? (size_t)h.total_len : 0;
+}
+
+// density_hip_parity and density_hip_parity2: they differ in the blob's version
+size_t parity_staged(uint8_t version, const uint8_t* input, size_t input_size, size_t chunk_size, uint32_t n_groups, uint8_t* parity, size_t parity_capacity) {
+    g_last_error.clear();
+    const size_t need = parity_size_of(version, input_size, chunk_size, n_groups);
+    if (!need || (!input && input_size) || !parity) { set_error("bad argument"); return 0; }
+    if (parity_capacity < need) { set_error("parity capacity below density_hip_parity_size() / density_hip_parity2_size()"); return 0; }
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipError_t e = ensure_staging(c, input_size, need, 0);
+    if (e == hipSuccess) e = copy_host_side_pinned(c->stage_in.p, input, input_size, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) { set_error("staging (H2D)", e); return 0; }
+    e = launch_parity_rows((const uint8_t*)c->stage_in.p, make_parity_header(input_size, chunk_size, n_groups, version), (uint8_t*)c->stage_out.p, c->stream);
+    if (e != hipSuccess) { set_error("kernel launch (parity)", e); return 0; }
+    e = copy_host_side_pinned(parity, c->stage_out.p, need, hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) { set_error("staging (D2H)", e); return 0; }
+    return need;
 }
 }  // namespace
 
@@ -335,21 +354,10 @@ size_t density_hip_decode_recover(const uint8_t* container, size_t container_siz
 }
 
 size_t density_hip_parity(const uint8_t* input, size_t input_size, size_t chunk_size, uint32_t n_groups, uint8_t* parity, size_t parity_capacity) {
-    g_last_error.clear();
-    const size_t need = density_hip_parity_size(input_size, chunk_size, n_groups);
-    if (!need || (!input && input_size) || !parity) { set_error("bad argument"); return 0; }
-    if (parity_capacity < need) { set_error("parity capacity below density_hip_parity_size()"); return 0; }
-    DeviceCtx* c = acquire_ctx();
-    if (!c) return 0;
-    std::lock_guard<std::mutex> lk(c->mu);
-    hipError_t e = ensure_staging(c, input_size, need, 0);
-    if (e == hipSuccess) e = copy_host_side_pinned(c->stage_in.p, input, input_size, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) { set_error("staging (H2D)", e); return 0; }
-    e = launch_parity_rows((const uint8_t*)c->stage_in.p, make_parity_header(input_size, chunk_size, n_groups), (uint8_t*)c->stage_out.p, c->stream);
-    if (e != hipSuccess) { set_error("kernel launch (parity)", e); return 0; }
-    e = copy_host_side_pinned(parity, c->stage_out.p, need, hipMemcpyDeviceToHost, c->stream);
-    if (e != hipSuccess) { set_error("staging (D2H)", e); return 0; }
-    return need;
+    return parity_staged(1, input, input_size, chunk_size, n_groups, parity, parity_capacity);
+}
+size_t density_hip_parity2(const uint8_t* input, size_t input_size, size_t chunk_size, uint32_t n_groups, uint8_t* parity, size_t parity_capacity) {
+    return parity_staged(2, input, input_size, chunk_size, n_groups, parity, parity_capacity);
 }
 
 }  // extern "C"

@@ -111,12 +111,15 @@ inline size_t trailer_bytes(size_t n_chunks) { return align_up(4 * n_chunks, 16)
 inline size_t header_trailer(const density_hip_header_t& h) { return (h.flags & DENSITY_HIP_FLAG_CHECKSUM) ? trailer_bytes(h.n_chunks) : 0; }
 inline size_t seal_overhead(size_t n_chunks) { return 16 + trailer_bytes(n_chunks); }
 // the parity blob "DHP1" of an input of n bytes cut every `chunk` (valid) bytes, `requested` groups asked for: its header (n_chunks must fit 32 bits), its size
-inline density_hip_parity_header_t make_parity_header(size_t n, size_t chunk, uint32_t requested) {
+// (version 1: the P rows; version 2: as many Q rows behind them), and the longest group — version 2 takes 255 members: 2 has order 255 in GF(2^8)
+inline density_hip_parity_header_t make_parity_header(size_t n, size_t chunk, uint32_t requested, uint8_t version = 1) {
     const size_t n_chunks = chunk_count(n, chunk);
-    return density_hip_parity_header_t{DENSITY_HIP_PARITY_MAGIC, 1, 0, 0, (uint32_t)chunk, (uint32_t)n_chunks, n, (uint32_t)std::min<size_t>(requested, n_chunks),
+    return density_hip_parity_header_t{DENSITY_HIP_PARITY_MAGIC, version, 0, 0, (uint32_t)chunk, (uint32_t)n_chunks, n, (uint32_t)std::min<size_t>(requested, n_chunks),
                                        (uint32_t)align_up(std::min(n, chunk), 16)};
 }
-inline size_t parity_bytes(const density_hip_parity_header_t& ph) { return sizeof(ph) + (size_t)ph.n_groups * ph.row_bytes; }
+inline size_t parity_bytes(const density_hip_parity_header_t& ph) { return sizeof(ph) + (size_t)ph.version * ph.n_groups * ph.row_bytes; }
+inline size_t parity_group_members(const density_hip_parity_header_t& ph) { return ph.n_groups ? ((size_t)ph.n_chunks + ph.n_groups - 1) / ph.n_groups : 0; }
+constexpr size_t kParityQMembers = 255;
 // the scratch of a seal in a workspace: the error word, the geometry the device reads from the container's header, a word per chunk (of which an
 // input of n bytes has at most one per 256 bytes)
 struct SealPlan {
@@ -315,7 +318,8 @@ struct DecodePlan {
     uint32_t* err(uint8_t* ws) const { return reinterpret_cast<uint32_t*>(ws + off_err); }
     uint32_t* damaged(uint8_t* ws) const { return err(ws) + 1; }                        // (a verdict decode: the number of damaged chunks)
     uint32_t* recovered(uint8_t* ws) const { return err(ws) + 2; }                      // (a recover decode: the number of chunks rebuilt)
-    // (a recover decode, behind the verifying sum: that leaves its sums in the first word per chunk of `produced`; the second is free for a word per parity group)
+    // (a recover decode, behind the verifying sum: that leaves its sums in the first word per chunk of `produced`; the second is free for a word per parity group:
+    // parity.hip's plan word)
     uint32_t* victims(uint8_t* ws, uint32_t n_chunks) const { return reinterpret_cast<uint32_t*>(produced(ws)) + n_chunks; }
     uint64_t* sizes(uint8_t* ws) const { return reinterpret_cast<uint64_t*>(ws + off_sizes); }
     uint64_t* offsets(uint8_t* ws) const { return reinterpret_cast<uint64_t*>(ws + off_offsets); }
@@ -360,17 +364,20 @@ int run_decode_container(DeviceCtx* c, const uint8_t* d_in, size_t container_siz
                          size_t cap, uint8_t* ws, hipStream_t s, size_t* decoded_out, size_t ws_size = 0);
 // run_decode_container on a SEALED container, then a verdict word per chunk in d_verdicts, the count in p.damaged(ws) and, with DENSITY_HIP_SALVAGE_BLANK in
 // `flags`, zeros over the damaged chunks' output; damaged_out (host, nullable): synchronises and reports.  With `rec` (a recover decode) the chunks that are
-// the only damaged ones of their parity groups are rebuilt and verified again in between, their number goes to p.recovered(ws), and the code returned is
+// the only damaged ones of their parity groups — with Q rows: the only one or two — are rebuilt and verified again in between, their number goes to p.recovered(ws), and the code returned is
 // DENSITY_HIP_OK wherever no chunk remains damaged; rec->recovered_out (host, nullable) synchronises as damaged_out does.
 struct Recovery {
     const uint8_t* d_rows;            // the blob's rows on the device (behind its header), checked against the container by check_parity_header
     uint32_t n_groups, row_bytes;
+    bool with_q;                      // a version-2 blob: n_groups Q rows behind the n_groups P rows
     uint32_t* recovered_out;
 };
 int run_decode_verdicts(DeviceCtx* c, const uint8_t* d_in, size_t container_size, const density_hip_header_t& h, uint8_t* d_out, size_t cap, uint8_t* ws,
                         hipStream_t s, size_t ws_size, uint32_t* d_verdicts, unsigned flags, uint32_t* damaged_out, const Recovery* rec = nullptr);
 // a parity blob's header against the container it is to serve and the bytes there are of it: DENSITY_HIP_OK / _ERR_FORMAT / _ERR_ARGUMENT (include/density_hip.h)
 int check_parity_header(const density_hip_parity_header_t& ph, const density_hip_header_t& h, size_t parity_size);
+// density_hip_parity_size (version 1) and density_hip_parity2_size (version 2)
+size_t parity_size_of(uint8_t version, size_t input_size, size_t chunk_size, uint32_t n_groups);
 // the seal of the container just encoded for d_in (`ws`: plan_seal(n).total bytes); `header`: the caller's copy of its header, or nullptr
 int run_seal_container(DeviceCtx* c, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, const density_hip_header_t* header, uint8_t* ws, hipStream_t s,
                        density_hip_header_t* header_out);

@@ -204,15 +204,18 @@ hipError_t launch_seal(const uint8_t* d_in, uint64_t input_size, uint8_t* d_cont
 hipError_t launch_move_trailer(const uint8_t* d_trailer, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err, hipStream_t stream);
 
 // ---- parity.hip (recovery records: the parity blob "DHP1" of include/density_hip.h, and the rebuild behind a verdict decode) ----
-// The blob of d_data (hdr.total_len bytes, any alignment) into d_blob (any alignment): hdr itself, then hdr.n_groups rows of hdr.row_bytes bytes.
+// The blob of d_data (hdr.total_len bytes, any alignment) into d_blob (any alignment): hdr itself, then hdr.n_groups rows of hdr.row_bytes bytes — with
+// hdr.version 2 as many Q rows (GF(2^8), from the same loads) behind them.
 hipError_t launch_parity_rows(const uint8_t* d_data, const density_hip_parity_header_t& hdr, uint8_t* d_blob, hipStream_t stream);
 // Behind launch_chunk_verdicts.  d_victim[g] (n_groups words of scratch) = the only chunk of group g with verdict DENSITY_HIP_CHUNK_DAMAGED, if there is exactly
 // one: its bytes in d_out become row g of d_rows (n_groups rows of row_bytes bytes, any alignment) XOR the other members' bytes, and d_acc[victim] = 0.
+// with_q (a version-2 blob: n_groups Q rows behind those; groups of at most 255): d_victim[g] names the group's only TWO damaged chunks as well, and both are
+// rebuilt from the two rows and the other members' bytes.  The same with_q goes to launch_recover_verify: it says how d_victim is read.
 hipError_t launch_recover_rebuild(uint8_t* d_out, uint64_t size, uint32_t chunk, uint32_t n_chunks, const uint8_t* d_rows, uint32_t n_groups, uint32_t row_bytes,
-                                  const uint32_t* d_verdicts, uint32_t* d_victim, uint32_t* d_acc, hipStream_t stream);
+                                  bool with_q, const uint32_t* d_verdicts, uint32_t* d_victim, uint32_t* d_acc, hipStream_t stream);
 // ... then the victims summed again into d_acc and held against the trailer d_expect: DENSITY_HIP_CHUNK_RECOVERED into d_verdicts where it matches now, one less in
 // *d_damaged and one more in *d_recovered (cleared here) for each.
-hipError_t launch_recover_verify(const uint8_t* d_out, uint64_t size, uint32_t chunk, uint32_t n_chunks, uint32_t n_groups, const uint32_t* d_victim, uint32_t* d_acc,
-                                 const uint8_t* d_expect, uint32_t* d_verdicts, uint32_t* d_damaged, uint32_t* d_recovered, hipStream_t stream);
+hipError_t launch_recover_verify(const uint8_t* d_out, uint64_t size, uint32_t chunk, uint32_t n_chunks, uint32_t n_groups, bool with_q, const uint32_t* d_victim,
+                                 uint32_t* d_acc, const uint8_t* d_expect, uint32_t* d_verdicts, uint32_t* d_damaged, uint32_t* d_recovered, hipStream_t stream);
 
 }  // namespace density

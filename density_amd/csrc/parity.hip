@@ -10,6 +10,12 @@
 //
 // Recovery never reads more than the verdict words to decide: recover_plan_kernel turns them into one word per group — the group's only damaged
 // member, or kNoVictim where it has none or several — and clears that chunk's accumulator; the kernels behind it leave at that word.
+//
+// Version 2 of the blob ("double parity") carries a second set of rows Q behind the first (P): Q row g = XOR of 2^j · D over the group's members, j the member's
+// place in its group, the product bytewise in GF(2^8) (polynomial 0x11D, generator 2).  The kernels that know it are the <true> instances of the templates
+// below; the <false> instances are the version-1 kernels.  One pass makes both rows: the members are walked from the last down and Q follows Horner's rule,
+// Q = 2·Q ^ D, on four packed bytes a word (xtime), so no member needs a constant of its own.  With both rows a group's plan word may name TWO damaged members
+// at places a < b, with the two constants of the solve  D_a = c1·Pxy ^ c2·Qxy,  D_b = Pxy ^ D_a  (Pxy, Qxy: the rows XOR the sums over the intact members).
 #include "checksum_dev.hpp"
 #include "kernels.hpp"
 
@@ -40,6 +46,20 @@ __device__ __forceinline__ u32x4 load16_clipped(const uint8_t* p, uint32_t off, 
     return v;
 }
 
+// GF(2^8) with polynomial 0x11D on the four bytes of a word (of each of four words): v times 2, and v times the constant c by shift-and-add
+__device__ __forceinline__ uint32_t xtime(uint32_t v) { return ((v & 0x7f7f7f7fu) << 1) ^ (((v >> 7) & 0x01010101u) * 0x1du); }
+__device__ __forceinline__ u32x4 xtime(u32x4 v) { return ((v & 0x7f7f7f7fu) << 1) ^ (((v >> 7) & 0x01010101u) * 0x1du); }
+template <class T>
+__device__ __forceinline__ T gf_times(uint32_t c, T v) {
+    T r = v ^ v;
+#pragma unroll
+    for (uint32_t bit = 0; bit < 8u; ++bit) {
+        r ^= v & (0u - ((c >> bit) & 1u));
+        v = xtime(v);
+    }
+    return r;
+}
+
 // acc[j] ^= the 16 bytes at off[j] (where off[j] < limit) of every chunk m of `data` with m % n_groups == g, but `skip`
 __device__ __forceinline__ void xor_members(u32x4 (&acc)[kParLoads], const uint32_t (&off)[kParLoads], uint32_t limit, const uint8_t* data, uint64_t size,
                                             uint32_t chunk, uint32_t n_chunks, uint32_t g, uint32_t n_groups, uint32_t skip) {
@@ -63,7 +83,46 @@ __device__ __forceinline__ uint8_t xor_members_byte(uint8_t b, uint32_t off, con
     return b;
 }
 
-// The blob of `data`: the header (work-group 0) and n_groups rows of hdr.row_bytes bytes behind it, every byte of them written.
+// Both rows at once: p[j] ^= D and q[j] = 2·q[j] ^ D for the members of group g from the LAST down, D as in xor_members — q ends as q·2^members ^ the XOR of
+// 2^place · D —; the members `skip_a` and `skip_b` count as zeros (they keep their places).
+__device__ __forceinline__ void horner_members(u32x4 (&p)[kParLoads], u32x4 (&q)[kParLoads], const uint32_t (&off)[kParLoads], uint32_t limit, const uint8_t* data,
+                                               uint64_t size, uint32_t chunk, uint32_t n_chunks, uint32_t g, uint32_t n_groups, uint32_t skip_a, uint32_t skip_b) {
+    const uint32_t members = (uint32_t)(((uint64_t)n_chunks - g + n_groups - 1u) / n_groups);
+#pragma unroll 2
+    for (uint32_t place = members; place-- > 0u;) {
+        const uint64_t m = g + (uint64_t)place * n_groups;
+#pragma unroll
+        for (uint32_t j = 0; j < kParLoads; ++j) q[j] = xtime(q[j]);
+        if (m == skip_a || m == skip_b) continue;
+        const uint32_t len = chunk_len(size, chunk, (uint32_t)m);
+        const uint8_t* d = data + m * chunk;
+        u32x4 v[kParLoads];
+#pragma unroll
+        for (uint32_t j = 0; j < kParLoads; ++j) v[j] = off[j] < limit ? load16_clipped(d, off[j], len) : u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+        for (uint32_t j = 0; j < kParLoads; ++j) {
+            p[j] ^= v[j];
+            q[j] ^= v[j];
+        }
+    }
+}
+// the same for one byte (in the low byte of p and q)
+__device__ __forceinline__ void horner_members_byte(uint32_t& p, uint32_t& q, uint32_t off, const uint8_t* data, uint64_t size, uint32_t chunk, uint32_t n_chunks, uint32_t g,
+                                                    uint32_t n_groups, uint32_t skip_a, uint32_t skip_b) {
+    const uint32_t members = (uint32_t)(((uint64_t)n_chunks - g + n_groups - 1u) / n_groups);
+    for (uint32_t place = members; place-- > 0u;) {
+        const uint64_t m = g + (uint64_t)place * n_groups;
+        q = xtime(q);
+        if (m == skip_a || m == skip_b || off >= chunk_len(size, chunk, (uint32_t)m)) continue;
+        const uint32_t b = data[m * chunk + off];
+        p ^= b;
+        q ^= b;
+    }
+}
+
+// The blob of `data`: the header (work-group 0) and n_groups rows of hdr.row_bytes bytes behind it — with kQ (hdr.version 2) the n_groups Q rows behind those, from
+// the same loads —, every byte of them written.
+template <bool kQ>
 __global__ __launch_bounds__(kParThreads) void parity_rows_kernel(const uint8_t* __restrict__ data, density_hip_parity_header_t hdr, uint8_t* __restrict__ blob) {
     const uint64_t size = hdr.total_len;
     const uint32_t chunk = hdr.chunk_size, n_chunks = hdr.n_chunks, n_groups = hdr.n_groups, row_bytes = hdr.row_bytes;
@@ -81,55 +140,156 @@ __global__ __launch_bounds__(kParThreads) void parity_rows_kernel(const uint8_t*
     const uint64_t units = (uint64_t)n_groups * tiles;
     for (uint64_t u = blockIdx.x; u < units; u += gridDim.x) {
         const uint32_t g = (uint32_t)(u / tiles), t0 = (uint32_t)(u % tiles) * kParTile;
-        u32x4 acc[kParLoads];
+        u32x4 acc[kParLoads], q[kParLoads];
         uint32_t off[kParLoads];
 #pragma unroll
         for (uint32_t j = 0; j < kParLoads; ++j) {
-            acc[j] = u32x4{0u, 0u, 0u, 0u};
+            acc[j] = q[j] = u32x4{0u, 0u, 0u, 0u};
             off[j] = t0 + (j * kParThreads + threadIdx.x) * 16u;
         }
-        xor_members(acc, off, row_bytes, data, size, chunk, n_chunks, g, n_groups, kNoVictim);
+        if (kQ) horner_members(acc, q, off, row_bytes, data, size, chunk, n_chunks, g, n_groups, kNoVictim, kNoVictim);
+        else xor_members(acc, off, row_bytes, data, size, chunk, n_chunks, g, n_groups, kNoVictim);
         uint8_t* row = blob + kHeaderBytes + (uint64_t)g * row_bytes;
 #pragma unroll
-        for (uint32_t j = 0; j < kParLoads; ++j)
-            if (off[j] < row_bytes) store16(row + off[j], acc[j]);               // (row_bytes is a multiple of 16: a slot that begins inside the row ends inside it)
+        for (uint32_t j = 0; j < kParLoads; ++j) {
+            if (off[j] >= row_bytes) continue;                               // (row_bytes is a multiple of 16: a slot that begins inside the row ends inside it)
+            store16(row + off[j], acc[j]);
+            if (kQ) store16(row + (uint64_t)n_groups * row_bytes + off[j], q[j]);
+        }
     }
 }
 
-// victim[g] = the only chunk of group g whose verdict is DENSITY_HIP_CHUNK_DAMAGED — its accumulator is cleared for the sum that follows the rebuild —,
-// kNoVictim where the group has none or more than one.  A work-group per group, in a grid-stride loop; the lanes share out the group's verdict words.
+// A group's plan word.  Version 1 (kQ false): the group's only damaged chunk.  Version 2: a | b << 8 | c1 << 16 | c2 << 24 — the places a <= b (below 255) of
+// its one (a == b, the constants 0) or two damaged members in the group, and for two the constants of the solve.  kNoVictim either way: nothing to rebuild.
+// victims_of: how many, and which chunks.
+template <bool kQ>
+__device__ __forceinline__ uint32_t victims_of(uint32_t word, uint32_t g, uint32_t n_groups, uint32_t (&k)[2]) {
+    if (word == kNoVictim) return 0u;
+    if (!kQ) { k[0] = k[1] = word; return 1u; }
+    const uint32_t a = word & 255u, b = (word >> 8) & 255u;
+    k[0] = g + a * n_groups;
+    k[1] = g + b * n_groups;
+    return a == b ? 1u : 2u;
+}
+// The word of the pair at places a < b < 255: with d = 2^(b-a) ^ 1 (not 0: 2 has order 255), c1 = 2^(b-a) / d and c2 = 2^(-a) / d, by the logarithm of d — a
+// walk along the powers of 2, once per group and by one lane.
+__device__ uint32_t gf_pow2(uint32_t e) {
+    uint32_t r = 1u;
+    for (; e; --e) r = xtime(r);
+    return r;
+}
+__device__ uint32_t pair_word(uint32_t a, uint32_t b) {
+    const uint32_t d = gf_pow2(b - a) ^ 1u;
+    uint32_t log_d = 0;
+    for (uint32_t r = 1u; r != d; r = xtime(r)) ++log_d;
+    const uint32_t c1 = gf_pow2((b - a + 255u - log_d) % 255u), c2 = gf_pow2((510u - a - log_d) % 255u);
+    return a | b << 8 | c1 << 16 | c2 << 24;
+}
+
+// victim[g] = group g's plan word: the only chunk of the group whose verdict is DENSITY_HIP_CHUNK_DAMAGED — with kQ: the only one or the only two —, kNoVictim where
+// there are none or more; the accumulators of the chunks it names are cleared for the sum that follows the rebuild.  A work-group per group, in a grid-stride
+// loop; the lanes share out the group's verdict words.
+template <bool kQ>
 __global__ __launch_bounds__(kParThreads) void recover_plan_kernel(const uint32_t* __restrict__ verdict, uint32_t n_chunks, uint32_t n_groups,
                                                                    uint32_t* __restrict__ victim, uint32_t* __restrict__ acc) {
-    __shared__ uint32_t s_count, s_who;
+    __shared__ uint32_t s_count, s_first, s_last;
     for (uint32_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
-        if (threadIdx.x == 0) s_count = s_who = 0u;
+        if (threadIdx.x == 0) { s_count = s_last = 0u; s_first = kNoVictim; }
         __syncthreads();
-        uint32_t count = 0, who = 0;
+        uint32_t count = 0, first = kNoVictim, last = 0;
         for (uint64_t m = g + (uint64_t)threadIdx.x * n_groups; m < n_chunks; m += (uint64_t)kParThreads * n_groups)
-            if (verdict[m] == DENSITY_HIP_CHUNK_DAMAGED) { ++count; who = (uint32_t)m; }
-        if (count) { atomicAdd(&s_count, count); atomicAdd(&s_who, who); }      // (s_who is read only where one lane found one chunk)
+            if (verdict[m] == DENSITY_HIP_CHUNK_DAMAGED) {
+                ++count;
+                first = first < (uint32_t)m ? first : (uint32_t)m;
+                last = (uint32_t)m;
+            }
+        if (count) { atomicAdd(&s_count, count); atomicMin(&s_first, first); atomicMax(&s_last, last); }
         __syncthreads();
         if (threadIdx.x == 0) {
-            const bool one = s_count == 1u;
-            victim[g] = one ? s_who : kNoVictim;
-            if (one) acc[s_who] = 0u;
+            uint32_t word = kNoVictim;
+            if (s_count == 1u) {
+                word = kQ ? (s_first - g) / n_groups * 0x101u : s_first;
+                acc[s_first] = 0u;
+            } else if (kQ && s_count == 2u) {
+                word = pair_word((s_first - g) / n_groups, (s_last - g) / n_groups);
+                acc[s_first] = acc[s_last] = 0u;
+            }
+            victim[g] = word;
         }
         __syncthreads();                                                     // (s_count is cleared again in the next trip)
     }
 }
 
+// One tile of a pair: group g's damaged members ka < kb (so ka is a whole chunk and the tile, which begins inside the chunk size, inside it; kb may be the ragged
+// last one), neither read, both written by the lane that holds their position: from zeros the walk gives the sums over the intact members, the rows make them
+// Pxy and Qxy, and D_a = c1·Pxy ^ c2·Qxy, D_b = Pxy ^ D_a.  The tile is cut as in recover_rebuild_kernel, by ka's address: kb's region is whole chunks away.
+// kb is written at its true length — where that ends inside a 16-byte slot, bytewise.
+__device__ __forceinline__ void rebuild_pair_tile(uint8_t* out, uint64_t size, uint32_t chunk, uint32_t n_chunks, const uint8_t* __restrict__ rows, uint32_t n_groups,
+                                                  uint32_t row_bytes, uint32_t g, uint32_t t0, uint32_t ka, uint32_t kb, uint32_t c1, uint32_t c2) {
+    const uint32_t len_b = chunk_len(size, chunk, kb);
+    const uint32_t n = chunk - t0 < kParTile ? chunk - t0 : kParTile, n_b = t0 >= len_b ? 0u : len_b - t0 < n ? len_b - t0 : n;
+    uint8_t *pa = out + (uint64_t)ka * chunk + t0, *pb = out + (uint64_t)kb * chunk + t0;
+    const uint8_t *prow = rows + (uint64_t)g * row_bytes + t0, *qrow = prow + (uint64_t)n_groups * row_bytes;   // (two chunks and more: row_bytes == chunk)
+    const uint32_t lead = (16u - (uint32_t)((uintptr_t)pa & 15u)) & 15u, head = lead < n ? lead : n;
+    const uint32_t full = (n - head) / 16u, tail_at = head + full * 16u;
+    const auto byte_at = [&](uint32_t i) {
+        uint32_t p = 0u, q = 0u;
+        horner_members_byte(p, q, t0 + i, out, size, chunk, n_chunks, g, n_groups, ka, kb);
+        p ^= prow[i];
+        q ^= qrow[i];
+        const uint32_t da = gf_times(c1, p) ^ gf_times(c2, q);
+        pa[i] = (uint8_t)da;
+        if (i < n_b) pb[i] = (uint8_t)(da ^ p);
+    };
+    if (threadIdx.x < head) byte_at(threadIdx.x);
+    u32x4 p[kParLoads], q[kParLoads];
+    uint32_t off[kParLoads];
+#pragma unroll
+    for (uint32_t j = 0; j < kParLoads; ++j) {
+        off[j] = t0 + head + 16u * (j * kParThreads + threadIdx.x);
+        p[j] = q[j] = u32x4{0u, 0u, 0u, 0u};
+    }
+    horner_members(p, q, off, t0 + tail_at, out, size, chunk, n_chunks, g, n_groups, ka, kb);
+#pragma unroll
+    for (uint32_t j = 0; j < kParLoads; ++j) {
+        const uint32_t i = j * kParThreads + threadIdx.x, at = head + 16u * i;
+        if (i >= full) continue;
+        p[j] ^= load16(prow + at);
+        q[j] ^= load16(qrow + at);
+        const u32x4 da = gf_times(c1, p[j]) ^ gf_times(c2, q[j]), db = da ^ p[j];
+        *reinterpret_cast<u32x4*>(pa + at) = da;
+        if (at + 16u <= n_b) *reinterpret_cast<u32x4*>(pb + at) = db;
+        else if (at < n_b) {
+            const uint32_t w[4] = {db.x, db.y, db.z, db.w};
+#pragma unroll
+            for (uint32_t b = 0; b < 16u; ++b)
+                if (at + b < n_b) pb[at + b] = (uint8_t)(w[b / 4u] >> (8u * (b % 4u)));
+        }
+    }
+    if (threadIdx.x < n - tail_at) byte_at(tail_at + threadIdx.x);
+}
+
 // Group g's victim k (recover_plan_kernel), where it has one: the bytes of k's region of `out` become row g XOR the regions of the group's other members, the
 // last chunk at its true length, `out` and the rows at any alignment.  Inside a tile, as in blank_chunks_kernel: bytes up to the first 16-byte boundary
 // of the ADDRESS (the other members' regions are whole chunks away: the same phase), 16-byte stores, bytes behind the last whole one.  `out` is read
-// and written, but never the same chunk: no other chunk of the group is rebuilt.
+// and written, but never the same chunk: no other chunk of the group is rebuilt.  With kQ a group may have a pair instead: rebuild_pair_tile, and the Q rows
+// are read for nothing else.
+template <bool kQ>
 __global__ __launch_bounds__(kParThreads) void recover_rebuild_kernel(uint8_t* out, uint64_t size, uint32_t chunk, uint32_t n_chunks, const uint8_t* __restrict__ rows,
                                                                       uint32_t n_groups, uint32_t row_bytes, const uint32_t* __restrict__ victim) {
     const uint32_t tiles = (chunk + kParTile - 1) / kParTile;
     const uint64_t units = (uint64_t)n_groups * tiles;
     for (uint64_t u = blockIdx.x; u < units; u += gridDim.x) {
         const uint32_t g = (uint32_t)(u / tiles), t0 = (uint32_t)(u % tiles) * kParTile;
-        const uint32_t k = victim[g];
-        if (k == kNoVictim) continue;
+        const uint32_t word = victim[g];
+        uint32_t ks[2];
+        const uint32_t count = victims_of<kQ>(word, g, n_groups, ks);
+        if (count == 0u) continue;
+        if (kQ && count == 2u) {
+            rebuild_pair_tile(out, size, chunk, n_chunks, rows, n_groups, row_bytes, g, t0, ks[0], ks[1], (word >> 16) & 255u, word >> 24);
+            continue;
+        }
+        const uint32_t k = ks[0];
         const uint32_t len = chunk_len(size, chunk, k);
         if (t0 >= len) continue;                                             // (the ragged last chunk)
         const uint32_t n = len - t0 < kParTile ? len - t0 : kParTile;
@@ -158,6 +318,7 @@ __global__ __launch_bounds__(kParThreads) void recover_rebuild_kernel(uint8_t* o
 }
 
 // The rebuilt chunks summed again, by checksum_tiles_kernel's tile: a work-group takes the tiles of the groups' victims in a grid-stride loop
+template <bool kQ>
 __global__ __launch_bounds__(kSumThreads) void recover_sum_kernel(const uint8_t* __restrict__ out, uint64_t size, uint32_t chunk, uint32_t n_groups,
                                                                   const uint32_t* __restrict__ victim, uint32_t* __restrict__ acc) {
     __shared__ uint32_t part[kSumThreads / 64];
@@ -165,61 +326,81 @@ __global__ __launch_bounds__(kSumThreads) void recover_sum_kernel(const uint8_t*
     const uint64_t units = (uint64_t)n_groups * tiles;
     for (uint64_t u = blockIdx.x; u < units; u += gridDim.x) {
         const uint32_t g = (uint32_t)(u / tiles), t0 = (uint32_t)(u % tiles) * kSumTile;
-        const uint32_t k = victim[g];
-        if (k == kNoVictim) continue;                                        // (the same for the whole work-group, like every test in front of sum_tile)
-        const uint32_t len = chunk_len(size, chunk, k);
-        if (t0 >= len) continue;
-        sum_tile(out + (uint64_t)k * chunk, len, t0, part, acc + k);
+        uint32_t ks[2];
+        const uint32_t count = victims_of<kQ>(victim[g], g, n_groups, ks);   // (the same for the whole work-group, like every test in front of sum_tile)
+        for (uint32_t v = 0; v < count; ++v) {
+            const uint32_t len = chunk_len(size, chunk, ks[v]);
+            if (t0 < len) sum_tile(out + (uint64_t)ks[v] * chunk, len, t0, part, acc + ks[v]);
+        }
     }
 }
 
 // ... and held against the trailer once more, a thread per group: a victim whose bytes now have the trailer's checksum becomes DENSITY_HIP_CHUNK_RECOVERED and
-// moves from *damaged to *recovered; one whose bytes have not (a damaged row, a damaged trailer entry) stays DENSITY_HIP_CHUNK_DAMAGED.
+// moves from *damaged to *recovered; one whose bytes have not (a damaged row, a damaged trailer entry) stays DENSITY_HIP_CHUNK_DAMAGED — each of a pair for itself.
+template <bool kQ>
 __global__ __launch_bounds__(256) void recover_verify_kernel(const uint32_t* __restrict__ acc, uint64_t size, uint32_t chunk, uint32_t n_groups,
                                                              const uint32_t* __restrict__ victim, const uint8_t* __restrict__ expect, uint32_t* __restrict__ verdict,
                                                              uint32_t* __restrict__ damaged, uint32_t* __restrict__ recovered) {
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
     if (g >= n_groups) return;
-    const uint32_t k = victim[g];
-    if (k == kNoVictim) return;
-    if (fmix32(acc[k] + chunk_len(size, chunk, k)) != ld32u(expect + 4ull * k)) return;
-    verdict[k] = DENSITY_HIP_CHUNK_RECOVERED;
-    atomicSub(damaged, 1u);
-    atomicAdd(recovered, 1u);
+    uint32_t ks[2];
+    const uint32_t count = victims_of<kQ>(victim[g], g, n_groups, ks);
+    for (uint32_t v = 0; v < count; ++v) {
+        const uint32_t k = ks[v];
+        if (fmix32(acc[k] + chunk_len(size, chunk, k)) != ld32u(expect + 4ull * k)) continue;
+        verdict[k] = DENSITY_HIP_CHUNK_RECOVERED;
+        atomicSub(damaged, 1u);
+        atomicAdd(recovered, 1u);
+    }
 }
 
 uint32_t grid_for(uint64_t units) { return (uint32_t)(units < 1 ? 1 : units < kParMaxGroups ? units : kParMaxGroups); }
+
+template <bool kQ>
+hipError_t recover_rebuild(uint8_t* d_out, uint64_t size, uint32_t chunk, uint32_t n_chunks, const uint8_t* d_rows, uint32_t n_groups, uint32_t row_bytes,
+                           const uint32_t* d_verdicts, uint32_t* d_victim, uint32_t* d_acc, hipStream_t stream) {
+    hipLaunchKernelGGL(recover_plan_kernel<kQ>, dim3(grid_for(n_groups)), dim3(kParThreads), 0, stream, d_verdicts, n_chunks, n_groups, d_victim, d_acc);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const uint64_t units = (uint64_t)n_groups * ((chunk + kParTile - 1) / kParTile);
+    hipLaunchKernelGGL(recover_rebuild_kernel<kQ>, dim3(grid_for(units)), dim3(kParThreads), 0, stream, d_out, size, chunk, n_chunks, d_rows, n_groups, row_bytes, d_victim);
+    return hipGetLastError();
+}
+
+template <bool kQ>
+hipError_t recover_verify(const uint8_t* d_out, uint64_t size, uint32_t chunk, uint32_t n_groups, const uint32_t* d_victim, uint32_t* d_acc, const uint8_t* d_expect,
+                          uint32_t* d_verdicts, uint32_t* d_damaged, uint32_t* d_recovered, hipStream_t stream) {
+    const uint64_t units = (uint64_t)n_groups * ((chunk + kSumTile - 1) / kSumTile);
+    hipLaunchKernelGGL(recover_sum_kernel<kQ>, dim3(grid_for(units)), dim3(kSumThreads), 0, stream, d_out, size, chunk, n_groups, d_victim, d_acc);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(recover_verify_kernel<kQ>, dim3((n_groups + 255u) / 256u), dim3(256), 0, stream, d_acc, size, chunk, n_groups, d_victim, d_expect, d_verdicts, d_damaged,
+                       d_recovered);
+    return hipGetLastError();
+}
 
 }  // namespace
 
 hipError_t launch_parity_rows(const uint8_t* d_data, const density_hip_parity_header_t& hdr, uint8_t* d_blob, hipStream_t stream) {
     const uint64_t units = (uint64_t)hdr.n_groups * ((hdr.row_bytes + kParTile - 1) / kParTile);
-    hipLaunchKernelGGL(parity_rows_kernel, dim3(grid_for(units)), dim3(kParThreads), 0, stream, d_data, hdr, d_blob);
+    if (hdr.version == 2) hipLaunchKernelGGL(parity_rows_kernel<true>, dim3(grid_for(units)), dim3(kParThreads), 0, stream, d_data, hdr, d_blob);
+    else hipLaunchKernelGGL(parity_rows_kernel<false>, dim3(grid_for(units)), dim3(kParThreads), 0, stream, d_data, hdr, d_blob);
     return hipGetLastError();
 }
 
-hipError_t launch_recover_rebuild(uint8_t* d_out, uint64_t size, uint32_t chunk, uint32_t n_chunks, const uint8_t* d_rows, uint32_t n_groups, uint32_t row_bytes,
+hipError_t launch_recover_rebuild(uint8_t* d_out, uint64_t size, uint32_t chunk, uint32_t n_chunks, const uint8_t* d_rows, uint32_t n_groups, uint32_t row_bytes, bool with_q,
                                   const uint32_t* d_verdicts, uint32_t* d_victim, uint32_t* d_acc, hipStream_t stream) {
     if (n_chunks == 0) return hipSuccess;
-    hipLaunchKernelGGL(recover_plan_kernel, dim3(grid_for(n_groups)), dim3(kParThreads), 0, stream, d_verdicts, n_chunks, n_groups, d_victim, d_acc);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const uint64_t units = (uint64_t)n_groups * ((chunk + kParTile - 1) / kParTile);
-    hipLaunchKernelGGL(recover_rebuild_kernel, dim3(grid_for(units)), dim3(kParThreads), 0, stream, d_out, size, chunk, n_chunks, d_rows, n_groups, row_bytes, d_victim);
-    return hipGetLastError();
+    return with_q ? recover_rebuild<true>(d_out, size, chunk, n_chunks, d_rows, n_groups, row_bytes, d_verdicts, d_victim, d_acc, stream)
+                  : recover_rebuild<false>(d_out, size, chunk, n_chunks, d_rows, n_groups, row_bytes, d_verdicts, d_victim, d_acc, stream);
 }
 
-hipError_t launch_recover_verify(const uint8_t* d_out, uint64_t size, uint32_t chunk, uint32_t n_chunks, uint32_t n_groups, const uint32_t* d_victim, uint32_t* d_acc,
-                                 const uint8_t* d_expect, uint32_t* d_verdicts, uint32_t* d_damaged, uint32_t* d_recovered, hipStream_t stream) {
-    hipError_t e = hipMemsetAsync(d_recovered, 0, sizeof(uint32_t), stream);
+hipError_t launch_recover_verify(const uint8_t* d_out, uint64_t size, uint32_t chunk, uint32_t n_chunks, uint32_t n_groups, bool with_q, const uint32_t* d_victim,
+                                 uint32_t* d_acc, const uint8_t* d_expect, uint32_t* d_verdicts, uint32_t* d_damaged, uint32_t* d_recovered, hipStream_t stream) {
+    const hipError_t e = hipMemsetAsync(d_recovered, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess || n_chunks == 0) return e;
-    const uint64_t units = (uint64_t)n_groups * ((chunk + kSumTile - 1) / kSumTile);
-    hipLaunchKernelGGL(recover_sum_kernel, dim3(grid_for(units)), dim3(kSumThreads), 0, stream, d_out, size, chunk, n_groups, d_victim, d_acc);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(recover_verify_kernel, dim3((n_groups + 255u) / 256u), dim3(256), 0, stream, d_acc, size, chunk, n_groups, d_victim, d_expect, d_verdicts, d_damaged,
-                       d_recovered);
-    return hipGetLastError();
+    return with_q ? recover_verify<true>(d_out, size, chunk, n_groups, d_victim, d_acc, d_expect, d_verdicts, d_damaged, d_recovered, stream)
+                  : recover_verify<false>(d_out, size, chunk, n_groups, d_victim, d_acc, d_expect, d_verdicts, d_damaged, d_recovered, stream);
 }
 
 }  // namespace density

@@ -303,28 +303,49 @@ size_t density_hip_decode_verdicts(const uint8_t* container, size_t container_si
  *     density_hip_auto_chunk_for() — or for n_groups == 0 with a non-empty input.  Pure host arithmetic.
  *   density_hip_parity_device: the blob of a device buffer, asynchronous on `stream`; d_input and d_parity at any byte alignment.  A parity_capacity below
  *     density_hip_parity_size() is DENSITY_HIP_ERR_CAPACITY at once, nothing written.  Profiling mark: "parity_rows".
- *   density_hip_parity: the same on host pointers, staged whole; returns the bytes written, 0 on failure. */
+ *   density_hip_parity: the same on host pointers, staged whole; returns the bytes written, 0 on failure.
+ *
+ * Version 2 of the blob ("double parity") adds a second row per group over GF(2^8), as the Q of a P+Q RAID-6, so that any TWO damaged chunks of a group can be
+ * rebuilt.  The header is the same 32 bytes with version 2 (reserved0 and reserved1 stay 0); with G = n_groups:
+ *     [0,32)                                   density_hip_parity_header_t, version 2
+ *     [32, 32 + G * row_bytes)                 P rows: byte for byte the rows of the version-1 blob of the same (input, chunk_size, n_groups)
+ *     [32 + G * row_bytes, 32 + 2*G*row_bytes) Q rows
+ * row_bytes, the clamp of n_groups and the zero padding are those of version 1.  Chunk i, a member of group g = i % G, has the place j = i / G in its group;
+ * Q row g = XOR over the group's members of 2^j · D_i, where D_i is chunk i zero-padded to row_bytes and the product is taken bytewise in GF(2^8) with the
+ * polynomial 0x11D and the generator 2.  Since 2^255 = 1 a group has at most 255 members: ceil(n_chunks / n_groups) > 255 is invalid geometry.  An input of
+ * zero bytes gives a bare header with version 2 and n_groups 0.  (How a CPU reader rebuilds one chunk and two: INTEGRATION.md.)
+ *   density_hip_parity2_size / density_hip_parity2_device / density_hip_parity2 mirror the three calls above — arguments, return convention, any alignment,
+ *     asynchrony, refusals —; the size is also 0, and the device call DENSITY_HIP_ERR_ARGUMENT, for a group of more than 255 members.  Profiling mark: "parity2_rows".
+ * Out of scope: a second attempt through Q for a single damaged chunk whose P row is itself damaged (one damaged chunk is rebuilt from P, Q is not read);
+ * three or more damaged chunks in one group; any container flag announcing a blob of either version. */
 #define DENSITY_HIP_PARITY_MAGIC 0x31504844u /* "DHP1" */
 typedef struct density_hip_parity_header {
     uint32_t magic;          /* DENSITY_HIP_PARITY_MAGIC */
-    uint8_t  version;        /* 1 */
+    uint8_t  version;        /* 1: P rows; 2: P rows, then Q rows */
     uint8_t  reserved0;      /* 0 */
     uint16_t reserved1;      /* 0 */
     uint32_t chunk_size;     /* of the input's cut, and of every container the blob serves */
     uint32_t n_chunks;       /* ceil(total_len / chunk_size) */
     uint64_t total_len;      /* bytes of input */
-    uint32_t n_groups;       /* rows in the blob: 1 .. n_chunks (0 for an empty input) */
+    uint32_t n_groups;       /* rows in the blob (version 2: of each kind): 1 .. n_chunks (0 for an empty input) */
     uint32_t row_bytes;      /* round_up(min(chunk_size, total_len), 16) */
 } density_hip_parity_header_t;
 size_t density_hip_parity_size(size_t input_size, size_t chunk_size, uint32_t n_groups);
 int density_hip_parity_device(const void* d_input, size_t input_size, size_t chunk_size, uint32_t n_groups, void* d_parity, size_t parity_capacity, void* stream);
 size_t density_hip_parity(const uint8_t* input, size_t input_size, size_t chunk_size, uint32_t n_groups, uint8_t* parity, size_t parity_capacity);
+size_t density_hip_parity2_size(size_t input_size, size_t chunk_size, uint32_t n_groups);
+int density_hip_parity2_device(const void* d_input, size_t input_size, size_t chunk_size, uint32_t n_groups, void* d_parity, size_t parity_capacity, void* stream);
+size_t density_hip_parity2(const uint8_t* input, size_t input_size, size_t chunk_size, uint32_t n_groups, uint8_t* parity, size_t parity_capacity);
 /* density_hip_decode_device_recover runs density_hip_decode_device_verdicts unchanged (the same kernels, the same workspace rules and sizes) and then, with the blob:
  *   - rebuild: for every group with exactly ONE damaged member k, chunk k's region of d_output is replaced by row g XOR the regions of the group's other
  *     members (the last chunk at its true length; no byte past total_len is written);
  *   - re-verify: chunk k is summed again and held against trailer entry k: a match makes its verdict DENSITY_HIP_CHUNK_RECOVERED, anything else (a damaged
  *     row, a damaged trailer entry) leaves it DENSITY_HIP_CHUNK_DAMAGED;
  *   - groups with two or more damaged members are left alone; DENSITY_HIP_SALVAGE_BLANK then zeroes whatever is STILL damaged.
+ * With a version-2 blob a group with exactly TWO damaged members, at places a < b, is rebuilt as well: over the group's intact members (neither damaged region is
+ * read) Pxy = P row ^ XOR D_j and Qxy = Q row ^ XOR 2^j · D_j, then with d = 2^(b-a) ^ 1:  D_a = (2^(b-a) / d) · Pxy ^ (2^(-a) / d) · Qxy,  D_b = Pxy ^ D_a, each
+ * written at its true length.  Each of the two is summed and held against its OWN trailer entry, so one may become RECOVERED while the other stays DAMAGED.  A
+ * group with one damaged member is rebuilt from its P row as with version 1 (Q is not read); groups with three or more are left alone.
  * So a verdict is not DENSITY_HIP_CHUNK_DAMAGED if and only if the region's bytes have the trailer's checksum.  *damaged_out = chunks still damaged,
  * *recovered_out = chunks rebuilt (both HOST, each optional; with either the call synchronises `stream`, with both NULL it is fully asynchronous and leaves the
  * two counts in the second and third 32-bit word of d_workspace where the caller passed one).  Returns DENSITY_HIP_OK when no chunk remains damaged — also where
@@ -334,7 +355,7 @@ size_t density_hip_parity(const uint8_t* input, size_t input_size, size_t chunk_
  *     small synchronous copy).
  *   - DENSITY_HIP_ERR_ARGUMENT, nothing written: an unsealed container, unknown bits in `flags`, a parity header whose chunk_size / n_chunks / total_len are not
  *     the container's.  DENSITY_HIP_ERR_FORMAT, nothing written: a wrong magic or version, n_groups outside 1 .. n_chunks, a row_bytes that is not the
- *     formula's, a parity_size short of header plus rows.
+ *     formula's, a parity_size short of header plus rows (version 2: plus both kinds of rows), a version-2 header with groups of more than 255 members.
  * density_hip_decode_recover is the host-pointer form, shaped like density_hip_decode_verdicts: it returns total_len if at least one chunk is not damaged and no
  * argument or capacity error occurred, else 0.
  * Profiling marks: those of density_hip_decode_device_verdicts up to "chunk_verdicts", then "recover_rebuild", "recover_verify" and, when blanking runs, "blank_chunks". */
