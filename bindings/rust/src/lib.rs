@@ -70,7 +70,8 @@ pub mod sealed {
 }
 
 /// include/density_hip.h section 2, the container forms on the device: a PAGED container (sealed or not) to the packed wire form, byte for byte what
-/// density_hip_encode_device (+ density_hip_seal_device) writes.  Device pointers and a hipStream_t: for a caller that already binds HIP.
+/// density_hip_encode_device (+ density_hip_seal_device) writes, and a window of a container's chunks as a packed container of its own.  Device pointers and a
+/// hipStream_t: for a caller that already binds HIP.
 pub mod forms {
     pub use crate::sealed::DensityHipHeader;
     pub const DENSITY_HIP_FLAG_PAGED: u16 = 4;
@@ -79,6 +80,14 @@ pub mod forms {
         pub fn density_hip_unpage_device(d_container: *const core::ffi::c_void, container_size: usize, header: *const DensityHipHeader, d_output: *mut core::ffi::c_void,
                                          output_capacity: usize, d_workspace: *mut core::ffi::c_void, workspace_size: usize, stream: *mut core::ffi::c_void,
                                          header_out: *mut DensityHipHeader) -> i32;
+        /// chunks [first_chunk, first_chunk + chunk_count) of a container of any form as a packed container of their own; a byte range is
+        /// density_hip_chunk_range, density_hip_slice_device, density_hip_decode_device and `skip` added to the output pointer
+        pub fn density_hip_chunk_range(header: *const DensityHipHeader, offset: u64, length: u64, first_chunk: *mut u32, chunk_count: *mut u32, skip: *mut u64) -> i32;
+        pub fn density_hip_slice_bound(header: *const DensityHipHeader, first_chunk: u32, chunk_count: u32) -> usize;
+        pub fn density_hip_slice_device(d_container: *const core::ffi::c_void, container_size: usize, header: *const DensityHipHeader, first_chunk: u32, chunk_count: u32,
+                                        d_output: *mut core::ffi::c_void, output_capacity: usize, d_workspace: *mut core::ffi::c_void, workspace_size: usize,
+                                        stream: *mut core::ffi::c_void, header_out: *mut DensityHipHeader) -> i32;
+        pub fn density_hip_slice(container: *const u8, container_size: usize, first_chunk: u32, chunk_count: u32, output: *mut u8, output_size: usize) -> usize;
     }
 }
 

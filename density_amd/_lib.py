@@ -104,6 +104,11 @@ SYMBOLS.update({
     "density_hip_encode_device_paged": (_I, [_I, _VP, _SZ, _VP, _SZ, _SZ, _VP, _SZ, _VP, ctypes.POINTER(Header)]),
     "density_hip_pack_device": (_I, [_VP, _SZ, ctypes.POINTER(Header), _VP, _SZ, _VP, _SZ, _VP, ctypes.POINTER(Header)]),
     "density_hip_unpage_device": (_I, [_VP, _SZ, ctypes.POINTER(Header), _VP, _SZ, _VP, _SZ, _VP, ctypes.POINTER(Header)]),
+    "density_hip_chunk_range": (_I, [ctypes.POINTER(Header), ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                     ctypes.POINTER(ctypes.c_uint64)]),
+    "density_hip_slice_bound": (_SZ, [ctypes.POINTER(Header), ctypes.c_uint32, ctypes.c_uint32]),
+    "density_hip_slice_device": (_I, [_VP, _SZ, ctypes.POINTER(Header), ctypes.c_uint32, ctypes.c_uint32, _VP, _SZ, _VP, _SZ, _VP, ctypes.POINTER(Header)]),
+    "density_hip_slice": (_SZ, [_VP, _SZ, ctypes.c_uint32, ctypes.c_uint32, _VP, _SZ]),
     "density_hip_stream_encode_device": (_I, [_I, _VP, _SZ, _VP, _SZ, _VP, ctypes.POINTER(_SZ)]),
     "density_hip_stream_decode_device": (_I, [_I, _VP, _SZ, _VP, _SZ, _VP, ctypes.POINTER(_SZ)]),
     "density_hip_set_profiling": (None, [_I]),

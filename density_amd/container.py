@@ -267,6 +267,110 @@ def unpage(blob):
     return out
 
 
+def chunk_range(header, offset, length):
+    """(first chunk, chunk count, skip) of the chunks that cover input bytes [offset, offset + length) of the container `header` describes: the range starts
+    `skip` bytes into what those chunks decode to.  Raises ValueError for length == 0, a range past total_len and a header that is not a container's."""
+    first, count, skip = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
+    if offset < 0 or length < 0 or offset >= 1 << 64 or length >= 1 << 64:
+        raise ValueError(f"no chunk range for bytes [{offset}, {offset} + {length})")
+    rc = _lib.lib().density_hip_chunk_range(ctypes.byref(header), offset, length, ctypes.byref(first), ctypes.byref(count), ctypes.byref(skip))
+    if rc != _lib.OK:
+        raise ValueError(f"no chunk range for bytes [{offset}, {offset} + {length}) of a container of {header.total_len} bytes")
+    return first.value, count.value, skip.value
+
+
+def slice_bound(header, first_chunk, chunk_count):
+    """The capacity slice_device asks for; 0 for a window that is not inside the container's chunks."""
+    if not (0 <= first_chunk < 1 << 32 and 0 <= chunk_count < 1 << 32):
+        return 0
+    return int(_lib.lib().density_hip_slice_bound(ctypes.byref(header), first_chunk, chunk_count))
+
+
+def slice_device(d_container, container_size, first_chunk, chunk_count, d_out, cap, header=None, stream=0, workspace=(0, 0), want_header=True):
+    """Chunks [first_chunk, first_chunk + chunk_count) of a container of any form (sealed or not) as a packed container of their own, on the device: for a
+    container this library made, byte for byte what encode_device (+ seal_device) writes for that part of the input.  Returns the slice's header
+    (synchronises, and a window the call cannot follow raises) or None."""
+    if not (0 <= first_chunk < 1 << 32 and 0 <= chunk_count < 1 << 32):
+        raise EncodeError(f"slice: no chunks [{first_chunk}, {first_chunk} + {chunk_count})")
+    hdr = _lib.Header() if want_header else None
+    rc = _lib.lib().density_hip_slice_device(d_container, container_size, ctypes.byref(header) if header is not None else None, first_chunk, chunk_count, d_out, cap,
+                                             workspace[0], workspace[1], stream, ctypes.byref(hdr) if want_header else None)
+    _check(rc, EncodeError)
+    return hdr
+
+
+def slice(container, first_chunk, chunk_count, output):
+    """slice_device on host buffers, staged whole: returns the bytes written to `output` (at least slice_bound() bytes)."""
+    ia, n, k1 = _ro(container)
+    oa, cap, k2 = _rw(output)
+    if not (0 <= first_chunk < 1 << 32 and 0 <= chunk_count < 1 << 32):
+        raise EncodeError(f"slice: no chunks [{first_chunk}, {first_chunk} + {chunk_count})")
+    r = _lib.lib().density_hip_slice(ia, n, first_chunk, chunk_count, oa, cap)
+    if r == 0:
+        raise EncodeError(_lib.last_error())
+    return r
+
+
+def _device_header(d_container):
+    """The 32 bytes at a device address, read back through torch (on its current stream)."""
+    import torch
+
+    class _View:
+        __cuda_array_interface__ = {"shape": (32,), "typestr": "|u1", "data": (int(d_container), False), "version": 2}
+    return parse_header(bytes(torch.as_tensor(_View(), device="cuda").cpu().numpy()))
+
+
+def decode_range_device(d_container, container_size, offset, length, header=None, stream=0, workspace=(0, 0)):
+    """Input bytes [offset, offset + length) of a container on the device, from the chunks that cover them and no others: chunk_range, slice_device into a
+    scratch tensor, decode_device of the slice into a tensor of the covering chunks' extent.  Returns the view [skip : skip + length] of that tensor (torch,
+    uint8, on the current device).  Damage in chunks outside the range does not matter; a sealed container's chunks inside it are verified (ChecksumError).
+    stream == 0 is the library's own stream, which is not ordered behind torch's: torch's current stream is synchronised first.  Raises ValueError for
+    length == 0 and a range past the end, DecodeError for a container the calls refuse."""
+    import torch
+    if container_size < 32:
+        raise DecodeError("not a container")
+    if stream == 0:
+        torch.cuda.current_stream().synchronize()
+    h = header if header is not None else _device_header(d_container)
+    first, count, skip = chunk_range(h, offset, length)
+    cap = slice_bound(h, first, count)
+    if cap == 0:
+        raise DecodeError("bad container header")
+    scratch = torch.empty(cap, dtype=torch.uint8, device="cuda")
+    try:
+        sh = slice_device(d_container, container_size, first, count, scratch.data_ptr(), cap, header=h, stream=stream, workspace=workspace)
+    except EncodeError as e:
+        raise DecodeError(str(e)) from None
+    out = torch.empty(sh.total_len, dtype=torch.uint8, device="cuda")
+    got = decode_device(scratch.data_ptr(), sh.container_len, out.data_ptr(), sh.total_len, header=sh, stream=stream, workspace=workspace)
+    if got != sh.total_len:
+        raise DecodeError(f"the slice decoded to {got} bytes, not {sh.total_len}")
+    return out[skip:skip + length]
+
+
+def decode_range(container, offset, length):
+    """Input bytes [offset, offset + length) of a host-resident container, as a numpy uint8 array: chunk_range, slice, decode.  Raises as decode_range_device."""
+    import numpy as np
+    ia, n, k = _ro(container)
+    if n < 32:
+        raise DecodeError("not a container")
+    h = parse_header(ctypes.string_at(ia, 32))
+    first, count, skip = chunk_range(h, offset, length)
+    cap = slice_bound(h, first, count)
+    if cap == 0:
+        raise DecodeError("bad container header")
+    part = np.empty(cap, dtype=np.uint8)
+    try:
+        used = slice(container, first, count, part)
+    except EncodeError as e:
+        raise DecodeError(str(e)) from None
+    sh = parse_header(part[:32].tobytes())
+    out = np.empty(sh.total_len, dtype=np.uint8)
+    if decode(part[:used], out) != sh.total_len:
+        raise DecodeError(f"the slice did not decode to {sh.total_len} bytes")
+    return out[skip:skip + length]
+
+
 def decode_device(d_container, container_size, d_out, cap, header=None, stream=0, workspace=(0, 0), sync=True):
     size = ctypes.c_size_t(0)
     rc = _lib.lib().density_hip_decode_device(d_container, container_size, ctypes.byref(header) if header is not None else None, d_out, cap,

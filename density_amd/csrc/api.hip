@@ -1,5 +1,5 @@
 // api.hip — the C ABI of libdensity_hip.so (include/density_hip.h), first of three units: per-device context, workspace plans, the
-// container's device-side drivers (encode in its three forms, decode, pack) and the device-pointer / bookkeeping entry points.
+// container's device-side drivers (encode in its three forms, decode, pack, unpage, slice) and the device-pointer / bookkeeping entry points.
 // (api_stream.hip: one reference stream, from device and from host pointers; api_host.hip: the host-pointer container calls.)  No CPU
 // codec lives here: every byte is produced by the gfx950 kernels, and every entry point fails (returns 0 / an error code) when no usable
 // HIP device is present.
@@ -133,14 +133,20 @@ size_t container_bound_paged(int algo, size_t n, size_t chunk) {
     return paged_pages_base(nc, n, chunk) + nc * (size_t)paged_pages_per_chunk(chunk) * kPageBytes;
 }
 
+bool header_is_containers(const density_hip_header_t& h) {
+    if (h.magic != DENSITY_HIP_MAGIC || h.version != 1 || !valid_algo(h.algo)) return false;
+    if (!valid_chunk(h.chunk_size)) return false;
+    if (h.n_chunks != chunk_count(h.total_len, h.chunk_size)) return false;
+    if (h.flags & ~(DENSITY_HIP_FLAG_BLOCK_INDEX | DENSITY_HIP_FLAG_SLOTTED | DENSITY_HIP_FLAG_PAGED | DENSITY_HIP_FLAG_CHECKSUM)) return false;
+    // pages: Chameleon with its block index
+    if ((h.flags & DENSITY_HIP_FLAG_PAGED) && (h.algo != DENSITY_HIP_CHAMELEON || (h.flags & (DENSITY_HIP_FLAG_BLOCK_INDEX | DENSITY_HIP_FLAG_SLOTTED)) != DENSITY_HIP_FLAG_BLOCK_INDEX)) return false;
+    return true;
+}
+
 int check_header(const density_hip_header_t& h, size_t container_size) {
-    if (h.magic != DENSITY_HIP_MAGIC || h.version != 1 || !valid_algo(h.algo)) return DENSITY_HIP_ERR_FORMAT;
-    if (!valid_chunk(h.chunk_size)) return DENSITY_HIP_ERR_FORMAT;
-    if (h.n_chunks != chunk_count(h.total_len, h.chunk_size)) return DENSITY_HIP_ERR_FORMAT;
-    if (h.flags & ~(DENSITY_HIP_FLAG_BLOCK_INDEX | DENSITY_HIP_FLAG_SLOTTED | DENSITY_HIP_FLAG_PAGED | DENSITY_HIP_FLAG_CHECKSUM)) return DENSITY_HIP_ERR_FORMAT;
+    if (!header_is_containers(h)) return DENSITY_HIP_ERR_FORMAT;
     const size_t trailer = header_trailer(h);                                      // a sealed container ends in its trailer: the form's own rules hold for what lies in front of it
-    if (h.flags & DENSITY_HIP_FLAG_PAGED) {                                        // pages: Chameleon with its block index, whole pages behind the directory
-        if (h.algo != DENSITY_HIP_CHAMELEON || (h.flags & (DENSITY_HIP_FLAG_BLOCK_INDEX | DENSITY_HIP_FLAG_SLOTTED)) != DENSITY_HIP_FLAG_BLOCK_INDEX) return DENSITY_HIP_ERR_FORMAT;
+    if (h.flags & DENSITY_HIP_FLAG_PAGED) {                                        // whole pages behind the directory
         const size_t pb = paged_pages_base(h.n_chunks, h.total_len, h.chunk_size);
         if (h.container_len > container_size || h.container_len < pb + trailer) return DENSITY_HIP_ERR_FORMAT;
         if ((h.container_len - trailer - pb) % kPageBytes != 0 || h.container_len - trailer - pb >= (1ull << 32)) return DENSITY_HIP_ERR_FORMAT;
@@ -148,6 +154,12 @@ int check_header(const density_hip_header_t& h, size_t container_size) {
     }
     if (h.container_len > container_size || h.container_len < payload_base(h.n_chunks, h.total_len, h.flags & DENSITY_HIP_FLAG_BLOCK_INDEX) + trailer) return DENSITY_HIP_ERR_FORMAT;
     return DENSITY_HIP_OK;
+}
+
+size_t slice_bound(const density_hip_header_t& h, uint32_t first, uint32_t count) {
+    if (!header_is_containers(h) || count == 0 || (uint64_t)first + count > h.n_chunks) return 0;
+    const size_t len = slice_len(h, first, count);
+    return container_bound(h.algo, len, h.chunk_size) + ((h.flags & DENSITY_HIP_FLAG_CHECKSUM) ? seal_overhead(count) : 0);
 }
 
 // ---- device-side drivers (ctx already acquired; `ws` points at a workspace of sufficient size) ----
@@ -463,6 +475,53 @@ int run_unpage_container(DeviceCtx* c, const uint8_t* d_in, const density_hip_he
     return DENSITY_HIP_OK;
 }
 
+// chunks [first, first + count) of a container of any form -> a packed container: the window's size-table entries, index bytes and trailer entries lie where the
+// host can say; where its streams lie the layout kernel finds out on the device and leaves there for the gather
+int run_slice_container(DeviceCtx* c, const uint8_t* d_in, const density_hip_header_t& h, uint32_t first, uint32_t count, uint8_t* d_out, size_t cap, uint8_t* ws,
+                        hipStream_t s, density_hip_header_t* header_out) {
+    const DecodePlan p = plan_decode(h.algo, h.n_chunks);
+    uint32_t* d_err = p.err(ws);
+    uint64_t *d_dst_off = p.sizes(ws), *d_src_off = p.offsets(ws), *d_run = p.offsets(ws) + h.n_chunks, *d_lens = p.produced(ws);
+    const bool with_index = h.flags & DENSITY_HIP_FLAG_BLOCK_INDEX, paged = h.flags & DENSITY_HIP_FLAG_PAGED;
+    const uint64_t stride = (h.flags & DENSITY_HIP_FLAG_SLOTTED) ? slot_stride(h.algo, h.chunk_size) : 0;
+    const uint64_t pbase = payload_base(h.n_chunks, h.total_len, with_index);          // (paged: the directory's base)
+    const size_t trailer = header_trailer(h), body_len = h.container_len - trailer;    // the streams and pages end in front of a sealed container's trailer
+    const size_t len = slice_len(h, first, count);
+    const density_hip_header_t out_h = make_header(h.algo, h.chunk_size, count, len, h.flags & DENSITY_HIP_FLAG_BLOCK_INDEX);
+    const uint64_t out_base = payload_base(count, len, with_index);
+    Profiler prof(c, s);
+    hipError_t e = hipMemsetAsync(d_err, 0, sizeof(uint32_t), s);
+    const uint64_t dir_entry = 16ull * (paged_pages_per_chunk(h.chunk_size) + 1u), pages_base = paged ? paged_pages_base(h.n_chunks, h.total_len, h.chunk_size) : 0;
+    if (paged) {
+        // the directory check on the window's chunks alone: its chunk 0 is chunk `first` — the size table is read at d_in + 4 * first, the directory so
+        // much further on — and the input ends where the container's does
+        if (e == hipSuccess) e = launch_check_directory(d_in + 4ull * first, count, h.chunk_size, h.total_len - (uint64_t)first * h.chunk_size, pbase + (dir_entry - 4ull) * first,
+                                                        paged_pages_per_chunk(h.chunk_size), (uint32_t)((body_len - pages_base) / kPageBytes), d_lens, d_err, s);
+    }
+    if (e == hipSuccess) e = launch_slice_layout(d_in, body_len, h, first, count, pbase, stride, paged, d_out, cap, out_h, out_base, d_lens, d_src_off, d_dst_off, d_run, d_err, s);
+    if (e == hipSuccess && with_index) e = hipMemcpyAsync(d_out + index_base(count), d_in + index_base(h.n_chunks) + (uint64_t)first * h.chunk_size / 256, index_bytes(len, true), hipMemcpyDeviceToDevice, s);
+    prof.mark("slice_layout");
+    if (e == hipSuccess) {
+        if (paged) e = launch_unpage(d_in, count, pbase + dir_entry * first, pages_base, paged_pages_per_chunk(h.chunk_size), d_lens, d_dst_off, d_out, d_err, s);
+        else if (stride) e = launch_slice_gather(d_in, d_src_off, d_lens, d_dst_off, count, stride, d_out, d_err, s);
+        else e = launch_slice_gather(d_in, d_src_off, d_run, d_dst_off, 1, body_len - pbase, d_out, d_err, s);   // one run: the window's streams lie as the output wants them
+    }
+    prof.mark("slice_gather");
+    if (trailer) {
+        if (e == hipSuccess) e = launch_move_trailer(d_in + body_len + 4ull * first, d_out, cap, count, d_err, s);
+        prof.mark("move_trailer");
+    }
+    if (e != hipSuccess) { set_error("kernel launch (slice)", e); return DENSITY_HIP_ERR_RUNTIME; }
+    if (header_out) {
+        uint32_t h_err = 0;
+        e = read_back(s, d_err, &h_err, header_out, d_out, sizeof(*header_out));
+        if (e != hipSuccess) { set_error("slice (device)", e); return DENSITY_HIP_ERR_RUNTIME; }
+        if (h_err & 4u) { set_error("slice: a window the call cannot follow (size table, slots or page directory of its chunks)"); return DENSITY_HIP_ERR_FORMAT; }
+        if (h_err) { set_error("container does not fit the output capacity"); return DENSITY_HIP_ERR_CAPACITY; }
+    }
+    return DENSITY_HIP_OK;
+}
+
 // The seal of the container just written for d_in, in place: every chunk of the INPUT summed (checksum.hip), the trailer behind the container, the flag
 // and the new length in its header.  Where the container ends, and how the input was cut, is read from the header on the device, so that nothing here
 // waits for the encoder; the caller's copy of the header only lets the call refuse at once what the device would refuse.
@@ -616,6 +675,45 @@ int density_hip_unpage_device(const void* d_container, size_t container_size, co
     uint8_t* ws = nullptr;
     if (const int rc = resolve_workspace(c, d_workspace, workspace_size, need, need, &ws)) return rc;
     return run_unpage_container(c, (const uint8_t*)d_container, h, (uint8_t*)d_output, output_capacity, ws, s, header_out);
+}
+
+int density_hip_chunk_range(const density_hip_header_t* header, uint64_t offset, uint64_t length, uint32_t* first_chunk, uint32_t* chunk_count, uint64_t* skip) {
+    if (!header || !header_is_containers(*header) || !first_chunk || !chunk_count || !skip) return DENSITY_HIP_ERR_ARGUMENT;
+    if (length == 0 || offset > header->total_len || length > header->total_len - offset) return DENSITY_HIP_ERR_ARGUMENT;
+    const uint64_t first = offset / header->chunk_size, last = (offset + length - 1) / header->chunk_size;
+    *first_chunk = (uint32_t)first;
+    *chunk_count = (uint32_t)(last - first + 1);
+    *skip = offset - first * header->chunk_size;
+    return DENSITY_HIP_OK;
+}
+
+size_t density_hip_slice_bound(const density_hip_header_t* header, uint32_t first_chunk, uint32_t chunk_count) {
+    return header ? slice_bound(*header, first_chunk, chunk_count) : 0;
+}
+
+int density_hip_slice_device(const void* d_container, size_t container_size, const density_hip_header_t* header, uint32_t first_chunk, uint32_t chunk_count, void* d_output,
+                             size_t output_capacity, void* d_workspace, size_t workspace_size, void* stream, density_hip_header_t* header_out) {
+    g_last_error.clear();
+    if (!d_container || container_size < sizeof(density_hip_header_t) || !d_output || chunk_count == 0) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return DENSITY_HIP_ERR_RUNTIME;
+    std::lock_guard<std::mutex> lk(c->mu);
+    density_hip_header_t h;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (header) h = *header;
+    else {
+        hipError_t e = hipMemcpyAsync(&h, d_container, sizeof(h), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { set_error("header read-back", e); return DENSITY_HIP_ERR_RUNTIME; }
+    }
+    if (!header_is_containers(h)) { set_error("slice: not a container's header"); return DENSITY_HIP_ERR_ARGUMENT; }
+    if ((uint64_t)first_chunk + chunk_count > h.n_chunks) { set_error("slice: the window is not inside the container's chunks"); return DENSITY_HIP_ERR_ARGUMENT; }
+    if (output_capacity < slice_bound(h, first_chunk, chunk_count)) { set_error("output capacity below density_hip_slice_bound()"); return DENSITY_HIP_ERR_CAPACITY; }
+    if (check_header(h, container_size) != DENSITY_HIP_OK) { set_error("bad container header (its length, or its trailer's, against container_size)"); return DENSITY_HIP_ERR_FORMAT; }
+    const size_t need = plan_decode(h.algo, h.n_chunks).total;
+    uint8_t* ws = nullptr;
+    if (const int rc = resolve_workspace(c, d_workspace, workspace_size, need, need, &ws)) return rc;
+    return run_slice_container(c, (const uint8_t*)d_container, h, first_chunk, chunk_count, (uint8_t*)d_output, output_capacity, ws, s, header_out);
 }
 
 int density_hip_decode_device(const void* d_container, size_t container_size, const density_hip_header_t* header, void* d_output,

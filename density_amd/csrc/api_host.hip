@@ -353,6 +353,30 @@ size_t density_hip_decode_recover(const uint8_t* container, size_t container_siz
     return decode_verdicts_staged(container, container_size, parity, parity_size, output, output_size, verdicts, verdict_capacity, flags, damaged_out, recovered_out);
 }
 
+size_t density_hip_slice(const uint8_t* container, size_t container_size, uint32_t first_chunk, uint32_t chunk_count, uint8_t* output, size_t output_size) {
+    g_last_error.clear();
+    if (!container || container_size < sizeof(density_hip_header_t) || !output || chunk_count == 0) { set_error("bad argument"); return 0; }
+    density_hip_header_t h;
+    std::memcpy(&h, container, sizeof(h));
+    if (!header_is_containers(h)) { set_error("slice: not a container's header"); return 0; }
+    if ((uint64_t)first_chunk + chunk_count > h.n_chunks) { set_error("slice: the window is not inside the container's chunks"); return 0; }
+    const size_t bound = slice_bound(h, first_chunk, chunk_count);
+    if (output_size < bound) { set_error("output capacity below density_hip_slice_bound()"); return 0; }
+    if (check_header(h, container_size) != DENSITY_HIP_OK) { set_error("bad container header (its length, or its trailer's, against container_size)"); return 0; }
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    // staged whole, like every sealed container: the container up, the window's packed container down
+    hipError_t e = ensure_staging(c, h.container_len, bound, plan_decode(h.algo, h.n_chunks).total);
+    if (e == hipSuccess) e = copy_host_side_pinned(c->stage_in.p, container, h.container_len, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) { set_error("staging (H2D)", e); return 0; }
+    density_hip_header_t out_h;
+    if (run_slice_container(c, (const uint8_t*)c->stage_in.p, h, first_chunk, chunk_count, (uint8_t*)c->stage_out.p, bound, (uint8_t*)c->work.p, c->stream, &out_h) != DENSITY_HIP_OK) return 0;
+    e = copy_host_side_pinned(output, c->stage_out.p, out_h.container_len, hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) { set_error("staging (D2H)", e); return 0; }
+    return (size_t)out_h.container_len;
+}
+
 size_t density_hip_parity(const uint8_t* input, size_t input_size, size_t chunk_size, uint32_t n_groups, uint8_t* parity, size_t parity_capacity) {
     return parity_staged(1, input, input_size, chunk_size, n_groups, parity, parity_capacity);
 }

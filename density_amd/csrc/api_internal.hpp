@@ -344,6 +344,13 @@ const char* decode_kernel_name(int algo);
 size_t container_bound(int algo, size_t n, size_t chunk);
 size_t container_bound_slotted(int algo, size_t n, size_t chunk);
 int check_header(const density_hip_header_t& h, size_t container_size);
+// what check_header asks of a header before it looks at any length: magic, version, algorithm, chunk size and count, known flags, a paged form that exists
+bool header_is_containers(const density_hip_header_t& h);
+// the input bytes chunks [first, first + count) of a container cover, and density_hip_slice_bound(): 0 for a window that is not inside the container's chunks
+inline size_t slice_len(const density_hip_header_t& h, uint32_t first, uint32_t count) {
+    return (size_t)(std::min<uint64_t>(h.total_len, ((uint64_t)first + count) * h.chunk_size) - (uint64_t)first * h.chunk_size);
+}
+size_t slice_bound(const density_hip_header_t& h, uint32_t first, uint32_t count);
 
 // a container's header as the encoders hand it to the layout kernels (container_len: theirs to fill in)
 inline density_hip_header_t make_header(int algo, size_t chunk, size_t n_chunks, size_t total_len, uint32_t flags) {
@@ -381,6 +388,9 @@ size_t parity_size_of(uint8_t version, size_t input_size, size_t chunk_size, uin
 // the seal of the container just encoded for d_in (`ws`: plan_seal(n).total bytes); `header`: the caller's copy of its header, or nullptr
 int run_seal_container(DeviceCtx* c, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, const density_hip_header_t* header, uint8_t* ws, hipStream_t s,
                        density_hip_header_t* header_out);
+// chunks [first, first + count) of the container at d_in (header h: checked, the window inside it, cap >= slice_bound()) as a packed container at d_out
+int run_slice_container(DeviceCtx* c, const uint8_t* d_in, const density_hip_header_t& h, uint32_t first, uint32_t count, uint8_t* d_out, size_t cap, uint8_t* ws,
+                        hipStream_t s, density_hip_header_t* header_out);
 // ... of one reference stream (api_stream.hip)
 int run_stream_encode(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, uint8_t* ws, hipStream_t s, size_t* size_out);
 int run_stream_decode(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, uint8_t* ws, hipStream_t s, size_t* size_out);

@@ -279,6 +279,116 @@ __global__ __launch_bounds__(kCopyThreads) void unpage_kernel(const uint8_t* __r
     if (before + (uint64_t)bytes == size && chunk + 1u < n && t2 < ((0u - (uint32_t)end) & 15u)) out[end + t2] = 0;
 }
 
+// ---- chunks [first, first + count) of a container of any form -> a packed container of their own (density_hip_slice_device) ----
+__device__ __forceinline__ uint64_t safe_size_of(uint32_t algo, uint64_t n) {                    // (api_internal.hpp: safe_size)
+    const uint64_t b = algo == DENSITY_HIP_CHAMELEON ? 256 : algo == DENSITY_HIP_CHEETAH ? 128 : 64, s = algo == DENSITY_HIP_LION ? 6 : 8;
+    return n + (n / b) * s + ((n % b) ? s : 0);
+}
+
+// The window's layout, one work-group.  Where chunk `first`'s stream lies in a packed source only the size table says: the 16-byte-rounded entries are
+// scanned from chunk 0 on (tiles of kScanThreads, the carry of layout_common), from chunk `first` for the other forms (slotted: src_base + i * slot_stride;
+// paged: the gather follows the directory, which check_directory_kernel has held against the table — lens[k] comes from there, 0 where it refused).
+// Left on the device for the gather, per window chunk k: lens[k], src_off[k] (offset in `in`), dst_off[k] (offset in `out`: packed, from out_base), and
+// *run = the bytes from the first stream's start to the last one's end.  Written to `out` (any byte alignment): the header `hdr` with container_len = the
+// last stream's end, the window's size-table entries, zeros over the gaps in front of the payloads and between them.  Refused, with bit 4 of *err and then
+// no gap written and *run = 0: a window entry above its chunk's worst case or its slot, a window stream that ends behind `limit`.  Entries in front of the
+// window are summed, not judged.
+__global__ __launch_bounds__(kScanThreads) void slice_layout_kernel(const uint8_t* __restrict__ in, uint64_t limit, uint32_t algo, uint64_t chunk_bytes, uint64_t total_len,
+                                                                    uint32_t first, uint32_t count, uint64_t src_base, uint64_t slot_stride, uint32_t paged,
+                                                                    uint8_t* __restrict__ out, uint64_t capacity, density_hip_header_t hdr, uint64_t out_base,
+                                                                    uint64_t* lens, uint64_t* __restrict__ src_off, uint64_t* __restrict__ dst_off,
+                                                                    uint64_t* __restrict__ run, uint32_t* __restrict__ err) {
+    __shared__ uint64_t wave_sums[kScanThreads / 64];
+    __shared__ uint64_t s_first, s_end;
+    __shared__ uint32_t s_bad;
+    if (threadIdx.x == 0) { s_first = 0; s_end = 0; s_bad = *err; }                              // (paged: what the directory check raised)
+    __syncthreads();
+    const uint64_t from = (slot_stride || paged) ? first : 0u, to = (uint64_t)first + count;
+    uint64_t carry = 0;
+    for (uint64_t t0 = from; t0 < to; t0 += kScanThreads) {
+        const uint64_t i = t0 + threadIdx.x;
+        const bool in_window = i >= first && i < to;
+        uint64_t raw = 0, keep = 0;
+        if (i < to) {
+            keep = raw = ld32u(in + kHeaderBytes + 4ull * i);
+            if (in_window) {
+                const uint64_t at = i * chunk_bytes, len = total_len - at < chunk_bytes ? total_len - at : chunk_bytes;
+                if (paged) keep = lens[i - first];
+                else if (raw > safe_size_of(algo, len) || (slot_stride && raw > slot_stride)) { keep = 0; atomicOr(&s_bad, 4u); }
+            }
+        }
+        uint64_t tile_total = 0;
+        const uint64_t excl = carry + block_inclusive_scan(align16(keep), wave_sums, &tile_total) - align16(keep);
+        if (in_window) {
+            const uint64_t k = i - first;
+            const uint64_t so = paged ? 0ull : slot_stride ? src_base + i * slot_stride : src_base + excl;
+            if (!paged && (so > limit || keep > limit - so)) { keep = 0; atomicOr(&s_bad, 4u); }  // the stream runs past the container: the gather must not follow it
+            src_off[k] = so;
+            dst_off[k] = excl;                                                                   // (from the scan's start: made the output's below)
+            if (!paged) lens[k] = keep;
+            st32u(out + kHeaderBytes + 4ull * k, (uint32_t)raw);
+            if (k == 0) s_first = excl;
+            if (i == to - 1) s_end = excl + keep;
+        }
+        carry += tile_total;
+    }
+    __syncthreads();
+    const uint64_t end = out_base + (s_end - s_first);
+    const bool bad = s_bad != 0 || end > capacity;
+    for (uint64_t k = threadIdx.x; k < count; k += kScanThreads) {
+        const uint64_t d = out_base + (dst_off[k] - s_first), e = d + lens[k];
+        dst_off[k] = d;
+        if (!bad && k + 1 < count) for (uint64_t p = e; p < align16(e); ++p) out[p] = 0;         // the gap behind the stream is part of the container: zeros
+    }
+    if (threadIdx.x == 0) {
+        *run = bad ? 0ull : end - out_base;
+        if (bad) atomicOr(err, s_bad ? 4u : 2u);
+        const uint64_t len = bad ? out_base : end;
+        st32u(out, hdr.magic);
+        st32u(out + 4, (uint32_t)hdr.algo | (uint32_t)hdr.version << 8 | (uint32_t)hdr.flags << 16);
+        st32u(out + 8, hdr.chunk_size);
+        st32u(out + 12, hdr.n_chunks);
+        st32u(out + 16, (uint32_t)hdr.total_len);
+        st32u(out + 20, (uint32_t)(hdr.total_len >> 32));
+        st32u(out + 24, (uint32_t)len);
+        st32u(out + 28, (uint32_t)(len >> 32));
+    }
+    // (as in layout_encode_kernel: the gaps in front of the payloads are zeros)
+    const uint64_t table_end = kHeaderBytes + 4ull * count, ibase = (table_end + 15) / 16 * 16;
+    const uint64_t iend = ibase + ((hdr.flags & DENSITY_HIP_FLAG_BLOCK_INDEX) ? (hdr.total_len + 255) / 256 : 0);
+    if (threadIdx.x < ibase - table_end) out[table_end + threadIdx.x] = 0;
+    if (threadIdx.x >= 32 && threadIdx.x - 32 < out_base - iend) out[iend + threadIdx.x - 32] = 0;
+}
+
+// The gather of `runs` byte runs: run r is lens[r] bytes from in + src_off[r] to out + dst_off[r], both at any byte phase.  A packed source's window is ONE
+// run (its streams lie as the output wants them, gaps included: the three words are the layout kernel's src_off[0], *run and dst_off[0], read here, so the
+// host never learns them); a slotted source's is a run per chunk.  A run is cut into tiles of kCopyTile; work-groups take tiles in a grid-stride loop and
+// leave the tiles behind a run's end at once.  Inside a tile: bytes up to the first 16-byte boundary of the DESTINATION's address, 16-byte stores fed from
+// loads at whatever phase that gives the source, bytes behind the last whole one (blank_chunks_kernel's cut).  Nothing where *err is set.
+constexpr uint32_t kSliceMaxGroups = 256u * 32u;
+__global__ __launch_bounds__(kCopyThreads) void slice_gather_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ src_off, const uint64_t* __restrict__ lens,
+                                                                    const uint64_t* __restrict__ dst_off, uint32_t runs, uint64_t tiles_per_run, uint8_t* __restrict__ out,
+                                                                    const uint32_t* __restrict__ err) {
+    if (*err) return;
+    const uint64_t units = (uint64_t)runs * tiles_per_run;
+    for (uint64_t u = blockIdx.x; u < units; u += gridDim.x) {
+        const uint64_t r = u / tiles_per_run, t0 = (u % tiles_per_run) * kCopyTile, len = lens[r];
+        if (t0 >= len) continue;
+        const uint32_t n = len - t0 < kCopyTile ? (uint32_t)(len - t0) : kCopyTile;
+        const uint8_t* s = in + src_off[r] + t0;
+        uint8_t* d = out + dst_off[r] + t0;
+        const uint32_t lead = (0u - (uint32_t)(uintptr_t)d) & 15u, head = lead < n ? lead : n;
+        const uint32_t full = (n - head) / 16u, tail_at = head + 16u * full;                     // (full <= 1024: four stores a lane cover it)
+        u32x4 v[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) { const uint32_t i = j * kCopyThreads + threadIdx.x; if (i < full) v[j] = *reinterpret_cast<const u32x4_u*>(s + head + 16ull * i); }
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) { const uint32_t i = j * kCopyThreads + threadIdx.x; if (i < full) *reinterpret_cast<u32x4*>(d + head + 16ull * i) = v[j]; }
+        if (threadIdx.x < head) d[threadIdx.x] = s[threadIdx.x];
+        if (threadIdx.x < n - tail_at) d[tail_at + threadIdx.x] = s[tail_at + threadIdx.x];
+    }
+}
+
 // LDS ordering assumptions of chameleon.hip, checked on the device the library is running on.
 __global__ __launch_bounds__(64) void selftest_kernel(uint32_t* __restrict__ fail) {
     __shared__ __attribute__((aligned(16))) uint16_t cells[256];
@@ -381,6 +491,23 @@ hipError_t launch_unpage(const uint8_t* d_container, uint32_t n_chunks, uint64_t
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(unpage_kernel, dim3((uint32_t)blocks), dim3(kCopyThreads), 0, stream, d_container, dir_base, pages_base, pages_per_chunk, n_chunks,
                        d_sizes, d_offsets, d_out, d_err);
+    return hipGetLastError();
+}
+
+hipError_t launch_slice_layout(const uint8_t* d_container, uint64_t limit, const density_hip_header_t& src, uint32_t first, uint32_t count, uint64_t src_base,
+                               uint64_t slot_stride, bool paged, uint8_t* d_out, uint64_t capacity, density_hip_header_t hdr, uint64_t out_base, uint64_t* d_lens,
+                               uint64_t* d_src_off, uint64_t* d_dst_off, uint64_t* d_run, uint32_t* d_err, hipStream_t stream) {
+    hipLaunchKernelGGL(slice_layout_kernel, dim3(1), dim3(kScanThreads), 0, stream, d_container, limit, (uint32_t)src.algo, (uint64_t)src.chunk_size, src.total_len, first,
+                       count, src_base, slot_stride, paged ? 1u : 0u, d_out, capacity, hdr, out_base, d_lens, d_src_off, d_dst_off, d_run, d_err);
+    return hipGetLastError();
+}
+
+hipError_t launch_slice_gather(const uint8_t* d_container, const uint64_t* d_src_off, const uint64_t* d_lens, const uint64_t* d_dst_off, uint32_t runs,
+                               uint64_t longest_run, uint8_t* d_out, const uint32_t* d_err, hipStream_t stream) {
+    const uint64_t tiles = (longest_run + kCopyTile - 1) / kCopyTile, units = tiles * runs;
+    if (units == 0) return hipSuccess;
+    hipLaunchKernelGGL(slice_gather_kernel, dim3((uint32_t)(units < kSliceMaxGroups ? units : kSliceMaxGroups)), dim3(kCopyThreads), 0, stream, d_container, d_src_off,
+                       d_lens, d_dst_off, runs, tiles, d_out, d_err);
     return hipGetLastError();
 }
 

@@ -180,6 +180,17 @@ hipError_t launch_check_directory(const uint8_t* d_container, uint32_t n_chunks,
 // gaps between the streams included; nothing where *d_err is set.
 hipError_t launch_unpage(const uint8_t* d_container, uint32_t n_chunks, uint64_t dir_base, uint64_t pages_base, uint32_t pages_per_chunk,
                          const uint64_t* d_sizes, const uint64_t* d_offsets, uint8_t* d_out, const uint32_t* d_err, hipStream_t stream);
+// Chunks [first, first + count) of a container -> a packed container (density_hip_slice_device).  The layout, one work-group: `src` is the source's header,
+// `limit` where its streams end, src_base its payload base (packed: the size table is scanned from chunk 0 for the window's place; slot_stride != 0: slotted;
+// paged: d_lens[k] holds what launch_check_directory left for window chunk k).  Into d_out: `hdr` with its container_len, the window's size-table entries, the
+// zero gaps.  For the gather, count words each: d_lens, d_src_off, d_dst_off, and *d_run = the bytes from the first stream's start to the last one's end.
+// Bit 4 of *d_err: a window entry above its chunk's worst case or slot, a window stream behind `limit` (entries in front of the window are not judged).
+hipError_t launch_slice_layout(const uint8_t* d_container, uint64_t limit, const density_hip_header_t& src, uint32_t first, uint32_t count, uint64_t src_base,
+                               uint64_t slot_stride, bool paged, uint8_t* d_out, uint64_t capacity, density_hip_header_t hdr, uint64_t out_base, uint64_t* d_lens,
+                               uint64_t* d_src_off, uint64_t* d_dst_off, uint64_t* d_run, uint32_t* d_err, hipStream_t stream);
+// `runs` byte runs, d_lens[r] bytes (at most longest_run) from d_container + d_src_off[r] to d_out + d_dst_off[r], any alignment of either; nothing where *d_err is set
+hipError_t launch_slice_gather(const uint8_t* d_container, const uint64_t* d_src_off, const uint64_t* d_lens, const uint64_t* d_dst_off, uint32_t runs,
+                               uint64_t longest_run, uint8_t* d_out, const uint32_t* d_err, hipStream_t stream);
 // LDS same-address ordering self-test (ascending lane order within one ds instruction). *d_fail != 0 on violation.
 hipError_t launch_selftest(uint32_t* d_fail, hipStream_t stream);
 

@@ -236,6 +236,42 @@ int density_hip_pack_device(const void* d_container, size_t container_size, cons
  *     unwritten).  With header_out the call synchronises, returns the packed container's header and reports DENSITY_HIP_ERR_FORMAT / _CAPACITY. */
 int density_hip_unpage_device(const void* d_container, size_t container_size, const density_hip_header_t* header, void* d_output,
                               size_t output_capacity, void* d_workspace, size_t workspace_size, void* stream, density_hip_header_t* header_out);
+/* Slice: chunks [first_chunk, first_chunk + chunk_count) of a container as a container of their own — random access without touching a decoder.  The input is
+ * a packed, slotted or PAGED container of any algorithm, sealed or not; the output is an ordinary PACKED container: magic, algo, version and chunk_size copied,
+ * n_chunks = chunk_count, total_len = L = min(total_len, (first + count) * chunk_size) - first * chunk_size, flags = the source's DENSITY_HIP_FLAG_BLOCK_INDEX and
+ * DENSITY_HIP_FLAG_CHECKSUM and nothing else; behind it size-table entries first .. first+count-1, the block-index bytes [first * chunk_size / 256, + ceil(L / 256)),
+ * the payloads at 16-byte boundaries with zero gaps, container_len, and for a sealed source, behind round_up(E, 16), trailer entries first .. first+count-1,
+ * zero-padded.  Every byte up to container_len is written: byte for byte the packed container the layout above describes for those chunk streams — for a container
+ * this library made, what density_hip_encode_device() (+ density_hip_seal_device()) writes for input[first * chunk_size : + L] with the same chunk_size.  Every call
+ * that takes a container takes the result: decode, verdicts, pack, the multi-rank wire form.  Both buffers at ANY byte alignment: streams are moved, not parsed.
+ * A byte range is slice + decode + a pointer offset (density_amd.container.decode_range_device):
+ *   density_hip_chunk_range: the chunks that cover input bytes [offset, offset + length), and *skip = offset - first_chunk * chunk_size, where the range starts in
+ *     the slice's decoded bytes.  length == 0, offset + length > total_len or a header that is not a container's: DENSITY_HIP_ERR_ARGUMENT.  Pure host arithmetic.
+ *   density_hip_slice_bound: the capacity the slice asks for: density_hip_container_bound(algo, L, chunk_size), plus density_hip_seal_overhead(L, chunk_size) for a
+ *     sealed header; 0 for chunk_count == 0, first_chunk + chunk_count > n_chunks or a header that is not a container's.  Pure host arithmetic.
+ *   density_hip_slice_device: workspace as for decode — density_hip_decode_workspace_size(n_chunks of the SOURCE) — or NULL.
+ *   - chunk_count == 0, first_chunk + chunk_count > n_chunks, a header that is not a container's: DENSITY_HIP_ERR_ARGUMENT, nothing written.
+ *   - output_capacity < density_hip_slice_bound(): DENSITY_HIP_ERR_CAPACITY at once, nothing written.
+ *   - a header or trailer that does not fit container_size: DENSITY_HIP_ERR_FORMAT at once, nothing written.
+ *   - DENSITY_HIP_ERR_FORMAT found on the device, by the layout kernel in front of the gather, and then no payload byte of the output is written: a size-table entry
+ *     of the window above {algo}_safe_encode_buffer_size of its chunk's input; a window whose streams run past the container (packed) or past their slot (slotted);
+ *     for a PAGED source every fault density_hip_unpage_device knows, in the directory entries of the window's chunks only.
+ *   - DAMAGE OUTSIDE THE WINDOW IS NOT THIS CALL'S BUSINESS: a chunk in front of or behind the window may have a directory nobody can follow, a lying size, a flipped
+ *     bit — the slice is made, and it is the slice of an intact container.  One exception cannot be seen without parsing streams: a lying size-table entry IN FRONT OF
+ *     a packed window moves the window (a packed stream's place is the sum of the entries before it).  The slice then holds wrong bytes; a sealed slice says so when
+ *     it is decoded.  (A packed source's window is moved in one run, with the gaps between its streams as they stand: zeros in every container of this format.)
+ *   - header_out == NULL: fully asynchronous, no host round trip — the source offset of chunk first_chunk stays on the device — and nothing is reported (a refused
+ *     window leaves the payloads unwritten).  With header_out the call synchronises, returns the slice's header and reports DENSITY_HIP_ERR_FORMAT / _CAPACITY.
+ *     `header` may be NULL: it is then read back first, as in density_hip_decode_device.
+ *   density_hip_slice: the host-pointer form, staged whole; returns the bytes written, 0 on failure with density_hip_last_error() set.
+ * Profiling marks: "slice_layout", "slice_gather" and, for a sealed source, "move_trailer".
+ * Out of scope: the parity blob "DHP1" cannot be sliced (its rows span the whole input: a slice wants a blob of its own, density_hip_parity_device of the decoded
+ * window); chunk lists that are not a range; a range decode at this level (it is the three calls above). */
+int density_hip_chunk_range(const density_hip_header_t* header, uint64_t offset, uint64_t length, uint32_t* first_chunk, uint32_t* chunk_count, uint64_t* skip);
+size_t density_hip_slice_bound(const density_hip_header_t* header, uint32_t first_chunk, uint32_t chunk_count);
+int density_hip_slice_device(const void* d_container, size_t container_size, const density_hip_header_t* header, uint32_t first_chunk, uint32_t chunk_count,
+                             void* d_output, size_t output_capacity, void* d_workspace, size_t workspace_size, void* stream, density_hip_header_t* header_out);
+size_t density_hip_slice(const uint8_t* container, size_t container_size, uint32_t first_chunk, uint32_t chunk_count, uint8_t* output, size_t output_size);
 /* `header` may be NULL: it is then read back from the device (one small synchronous copy). */
 int density_hip_decode_device(const void* d_container, size_t container_size, const density_hip_header_t* header,
                               void* d_output, size_t output_capacity, void* d_workspace, size_t workspace_size,
