@@ -70,11 +70,23 @@ pub mod sealed {
 }
 
 /// include/density_hip.h section 2, the container forms on the device: a PAGED container (sealed or not) to the packed wire form, byte for byte what
-/// density_hip_encode_device (+ density_hip_seal_device) writes, and a window of a container's chunks as a packed container of its own.  Device pointers and a
+/// density_hip_encode_device (+ density_hip_seal_device) writes, a window of a container's chunks as a packed container of its own, and the windows of several
+/// containers joined into one.  Device pointers and a
 /// hipStream_t: for a caller that already binds HIP.
 pub mod forms {
     pub use crate::sealed::DensityHipHeader;
     pub const DENSITY_HIP_FLAG_PAGED: u16 = 4;
+    pub const DENSITY_HIP_JOIN_MAX_PARTS: u32 = 64;
+    /// density_hip_join_part_t: a window of one container's chunks; `header` is a HOST copy of the container's first 32 bytes, chunk_count == 0 skips the part
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug)]
+    pub struct DensityHipJoinPart {
+        pub container: *const core::ffi::c_void,
+        pub container_size: usize,
+        pub header: *const DensityHipHeader,
+        pub first_chunk: u32,
+        pub chunk_count: u32,
+    }
     #[link(name = "density_hip")]
     extern "C" {
         pub fn density_hip_unpage_device(d_container: *const core::ffi::c_void, container_size: usize, header: *const DensityHipHeader, d_output: *mut core::ffi::c_void,
@@ -88,6 +100,13 @@ pub mod forms {
                                         d_output: *mut core::ffi::c_void, output_capacity: usize, d_workspace: *mut core::ffi::c_void, workspace_size: usize,
                                         stream: *mut core::ffi::c_void, header_out: *mut DensityHipHeader) -> i32;
         pub fn density_hip_slice(container: *const u8, container_size: usize, first_chunk: u32, chunk_count: u32, output: *mut u8, output_size: usize) -> usize;
+        /// the chunk windows of several containers (any forms; alike in algorithm, chunk size, block index and seal) as ONE packed container: append, the
+        /// replacement of single chunks, a multi-rank container's rows as one container
+        pub fn density_hip_join_bound(parts: *const DensityHipJoinPart, n_parts: u32) -> usize;
+        pub fn density_hip_join_workspace_size(n_parts: u32, n_chunks_out: u32) -> usize;
+        pub fn density_hip_join_device(parts: *const DensityHipJoinPart, n_parts: u32, d_output: *mut core::ffi::c_void, output_capacity: usize,
+                                       d_workspace: *mut core::ffi::c_void, workspace_size: usize, stream: *mut core::ffi::c_void, header_out: *mut DensityHipHeader) -> i32;
+        pub fn density_hip_join(parts: *const DensityHipJoinPart, n_parts: u32, output: *mut u8, output_size: usize) -> usize;
     }
 }
 

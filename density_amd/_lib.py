@@ -18,6 +18,7 @@ CHUNK_DAMAGED = 1       # DENSITY_HIP_CHUNK_DAMAGED: a verdict word
 CHUNK_RECOVERED = 2     # DENSITY_HIP_CHUNK_RECOVERED: a verdict word of the recover calls
 SALVAGE_BLANK = 1       # DENSITY_HIP_SALVAGE_BLANK: flags of the verdict calls
 PARITY_MAGIC = 0x31504844   # "DHP1"
+JOIN_MAX_PARTS = 64          # DENSITY_HIP_JOIN_MAX_PARTS
 
 
 class Header(ctypes.Structure):
@@ -54,6 +55,12 @@ class MultiHeader(ctypes.Structure):
 class MultiRow(ctypes.Structure):
     """density_hip_multi_row_t"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("offset", "length", "input_bytes")]
+
+
+class JoinPart(ctypes.Structure):
+    """density_hip_join_part_t"""
+    _fields_ = [("container", ctypes.c_void_p), ("container_size", ctypes.c_size_t), ("header", ctypes.POINTER(Header)),
+                ("first_chunk", ctypes.c_uint32), ("chunk_count", ctypes.c_uint32)]
 
 
 _lib = None
@@ -109,6 +116,10 @@ SYMBOLS.update({
     "density_hip_slice_bound": (_SZ, [ctypes.POINTER(Header), ctypes.c_uint32, ctypes.c_uint32]),
     "density_hip_slice_device": (_I, [_VP, _SZ, ctypes.POINTER(Header), ctypes.c_uint32, ctypes.c_uint32, _VP, _SZ, _VP, _SZ, _VP, ctypes.POINTER(Header)]),
     "density_hip_slice": (_SZ, [_VP, _SZ, ctypes.c_uint32, ctypes.c_uint32, _VP, _SZ]),
+    "density_hip_join_bound": (_SZ, [ctypes.POINTER(JoinPart), ctypes.c_uint32]),
+    "density_hip_join_workspace_size": (_SZ, [ctypes.c_uint32, ctypes.c_uint32]),
+    "density_hip_join_device": (_I, [ctypes.POINTER(JoinPart), ctypes.c_uint32, _VP, _SZ, _VP, _SZ, _VP, ctypes.POINTER(Header)]),
+    "density_hip_join": (_SZ, [ctypes.POINTER(JoinPart), ctypes.c_uint32, _VP, _SZ]),
     "density_hip_stream_encode_device": (_I, [_I, _VP, _SZ, _VP, _SZ, _VP, ctypes.POINTER(_SZ)]),
     "density_hip_stream_decode_device": (_I, [_I, _VP, _SZ, _VP, _SZ, _VP, ctypes.POINTER(_SZ)]),
     "density_hip_set_profiling": (None, [_I]),

@@ -371,6 +371,84 @@ def decode_range(container, offset, length):
     return out[skip:skip + length]
 
 
+def _join_parts(parts, device):
+    """The JoinPart array of [(container, container_size, header or None, first_chunk, chunk_count), ...] and what keeps its pointers alive.  A None header is read
+    back from the device (device=True) or taken from the host array's first 32 bytes."""
+    keep, arr = [], (_lib.JoinPart * max(len(parts), 1))()
+    for i, (cont, size, header, first, count) in enumerate(parts):
+        if not (0 <= first < 1 << 32 and 0 <= count < 1 << 32):
+            raise EncodeError(f"join: no chunks [{first}, {first} + {count})")
+        if device:
+            addr = int(cont)
+            if header is None and count and addr and size >= 32:
+                header = _device_header(addr)
+        else:
+            addr, n, k = _ro(cont)
+            keep.append(k)
+            size = n if size is None else size
+            if header is None and count and n >= 32:
+                header = parse_header(ctypes.string_at(addr, 32))
+        keep.append(header)
+        arr[i] = _lib.JoinPart(addr, size, ctypes.pointer(header) if header is not None else None, first, count)
+    return arr, keep
+
+
+def join_bound(parts):
+    """The capacity join_device asks for parts [(d_container, container_size, header, first_chunk, chunk_count), ...]; 0 for a list the call refuses on the host."""
+    if not 0 < len(parts) <= _lib.JOIN_MAX_PARTS:
+        return 0
+    arr, keep = _join_parts(parts, True)
+    return int(_lib.lib().density_hip_join_bound(arr, len(parts)))
+
+
+def join_workspace_size(n_parts, n_chunks_out):
+    return int(_lib.lib().density_hip_join_workspace_size(n_parts, n_chunks_out))
+
+
+def join_device(parts, d_out, cap, stream=0, workspace=(0, 0), want_header=True):
+    """Chunk windows of several containers as ONE packed container, on the device: parts = [(d_container, container_size, header or None, first_chunk,
+    chunk_count), ...], each a window of a packed, slotted or paged container, sealed or not (all alike in algorithm, chunk size, block index and seal); a part
+    with chunk_count == 0 is skipped.  For containers this library made, byte for byte what encode_device (+ seal_device) writes for the windows' inputs one
+    behind the other.  A None header is read back first (on torch's current stream).  Returns the joined header (synchronises; a list the call refuses or
+    cannot follow raises) or None."""
+    if len(parts) > _lib.JOIN_MAX_PARTS:
+        raise EncodeError(f"join: {len(parts)} parts, at most {_lib.JOIN_MAX_PARTS}")
+    arr, keep = _join_parts(parts, True)
+    hdr = _lib.Header() if want_header else None
+    rc = _lib.lib().density_hip_join_device(arr, len(parts), d_out, cap, workspace[0], workspace[1], stream, ctypes.byref(hdr) if want_header else None)
+    _check(rc, EncodeError)
+    return hdr
+
+
+def join(parts, output):
+    """join_device on host arrays, staged whole: parts = [(container, first_chunk, chunk_count), ...]; returns the bytes written to `output`."""
+    oa, cap, k2 = _rw(output)
+    if len(parts) > _lib.JOIN_MAX_PARTS:
+        raise EncodeError(f"join: {len(parts)} parts, at most {_lib.JOIN_MAX_PARTS}")
+    arr, keep = _join_parts([(c, None, None, f, k) for c, f, k in parts], False)
+    r = _lib.lib().density_hip_join(arr, len(parts), oa, cap)
+    if r == 0:
+        raise EncodeError(_lib.last_error())
+    return r
+
+
+def replace_chunks_device(d_container, container_size, first_chunk, d_new, new_size, d_out, cap, header=None, new_header=None, stream=0, workspace=(0, 0),
+                          want_header=True):
+    """Container A with its chunks from first_chunk on replaced by the chunks of container B (same algorithm, chunk size, block index and seal; B is typically
+    the one-chunk container of a patched chunk): join(A[0, first), B, A[first + n_B, n_A)) into d_out.  B may reach or pass A's end — it is then the new end,
+    and first_chunk == n_A appends — but a B that ends in a ragged chunk in front of chunks A keeps raises, as does a first_chunk behind A's end."""
+    a = header if header is not None else _device_header(d_container)
+    b = new_header if new_header is not None else _device_header(d_new)
+    behind = first_chunk + b.n_chunks
+    if not 0 <= first_chunk <= a.n_chunks:
+        raise EncodeError(f"replace: no chunk {first_chunk} in a container of {a.n_chunks}")
+    if behind < a.n_chunks and b.total_len != b.n_chunks * b.chunk_size:
+        raise EncodeError("replace: the new chunks end in a ragged chunk, and chunks of the old container would follow it")
+    parts = [(d_container, container_size, a, 0, first_chunk), (d_new, new_size, b, 0, b.n_chunks),
+             (d_container, container_size, a, min(behind, a.n_chunks), max(a.n_chunks - behind, 0))]
+    return join_device(parts, d_out, cap, stream=stream, workspace=workspace, want_header=want_header)
+
+
 def decode_device(d_container, container_size, d_out, cap, header=None, stream=0, workspace=(0, 0), sync=True):
     size = ctypes.c_size_t(0)
     rc = _lib.lib().density_hip_decode_device(d_container, container_size, ctypes.byref(header) if header is not None else None, d_out, cap,

@@ -1,5 +1,5 @@
 // api.hip — the C ABI of libdensity_hip.so (include/density_hip.h), first of three units: per-device context, workspace plans, the
-// container's device-side drivers (encode in its three forms, decode, pack, unpage, slice) and the device-pointer / bookkeeping entry points.
+// container's device-side drivers (encode in its three forms, decode, pack, unpage, slice, join) and the device-pointer / bookkeeping entry points.
 // (api_stream.hip: one reference stream, from device and from host pointers; api_host.hip: the host-pointer container calls.)  No CPU
 // codec lives here: every byte is produced by the gfx950 kernels, and every entry point fails (returns 0 / an error code) when no usable
 // HIP device is present.
@@ -522,6 +522,119 @@ int run_slice_container(DeviceCtx* c, const uint8_t* d_in, const density_hip_hea
     return DENSITY_HIP_OK;
 }
 
+// ---- join: chunk windows of several containers as one packed container ----
+
+// what the host can say of a join before any byte moves: nullptr and *g, or why the part list is refused (include/density_hip.h: DENSITY_HIP_ERR_ARGUMENT)
+const char* join_geometry(const density_hip_join_part_t* parts, uint32_t n_parts, JoinGeometry* g) {
+    *g = JoinGeometry{};
+    if (!parts || n_parts == 0 || n_parts > DENSITY_HIP_JOIN_MAX_PARTS) return "join: 1 to DENSITY_HIP_JOIN_MAX_PARTS parts";
+    bool have = false, ragged = false;
+    for (uint32_t p = 0; p < n_parts; ++p) {
+        const density_hip_join_part_t& q = parts[p];
+        if (q.chunk_count == 0) continue;                                              // skipped: nothing of it is read
+        if (!q.container || !q.header || q.container_size < sizeof(density_hip_header_t)) return "join: a part without its container or without its header";
+        const density_hip_header_t& h = *q.header;
+        if (!header_is_containers(h)) return "join: not a container's header";
+        if ((uint64_t)q.first_chunk + q.chunk_count > h.n_chunks) return "join: a window that is not inside its container's chunks";
+        const uint32_t flags = h.flags & (DENSITY_HIP_FLAG_BLOCK_INDEX | DENSITY_HIP_FLAG_CHECKSUM);
+        if (!have) { g->algo = h.algo; g->chunk_size = h.chunk_size; g->flags = flags; have = true; }
+        else if (g->algo != h.algo || g->chunk_size != h.chunk_size || g->flags != flags) return "join: parts that differ in algorithm, chunk size, block index or seal";
+        if (ragged) return "join: a ragged chunk anywhere but at the output's end";
+        const uint64_t len = slice_len(h, q.first_chunk, q.chunk_count);
+        ragged = len != (uint64_t)q.chunk_count * h.chunk_size;
+        g->n_chunks += q.chunk_count;
+        g->total_len += len;
+        ++g->live;
+    }
+    if (!have) return "join: no chunks";
+    if (g->n_chunks > 0xffffffffull) return "join: more chunks than a header counts";
+    return nullptr;
+}
+
+size_t join_bound(const JoinGeometry& g) {
+    return container_bound(g.algo, g.total_len, g.chunk_size) + ((g.flags & DENSITY_HIP_FLAG_CHECKSUM) ? seal_overhead(g.n_chunks) : 0);
+}
+
+int check_join_parts(const density_hip_join_part_t* parts, uint32_t n_parts) {
+    for (uint32_t p = 0; p < n_parts; ++p)
+        if (parts[p].chunk_count && check_header(*parts[p].header, parts[p].container_size) != DENSITY_HIP_OK) {
+            set_error("join: bad container header (its length, or its trailer's, against container_size)");
+            return DENSITY_HIP_ERR_FORMAT;
+        }
+    return DENSITY_HIP_OK;
+}
+
+// The parts' windows -> one packed container: everything the host can say of a part — where its size table, index bytes, trailer entries and (slotted) streams
+// lie — goes into the part table, which travels with the launches; where a packed part's window lies the layout kernel finds out and leaves on the device.
+// A paged part goes through the directory check and the unpage gather as a slice does, handed offset pointers and its stretch of the join's run table.
+int run_join_container(DeviceCtx* c, const density_hip_join_part_t* parts, uint32_t n_parts, const JoinGeometry& g, uint8_t* d_out, size_t cap, uint8_t* ws,
+                       hipStream_t s, density_hip_header_t* header_out) {
+    const JoinPlan p = plan_join(g.n_chunks);
+    uint32_t* d_err = p.err(ws);
+    uint64_t *d_lens = p.lens(ws), *d_src = p.src(ws), *d_dst_off = p.dst_off(ws);
+    const bool with_index = g.flags & DENSITY_HIP_FLAG_BLOCK_INDEX, sealed = g.flags & DENSITY_HIP_FLAG_CHECKSUM;
+    const density_hip_header_t out_h = make_header(g.algo, g.chunk_size, g.n_chunks, g.total_len, g.flags & DENSITY_HIP_FLAG_BLOCK_INDEX);
+    const uint64_t out_base = payload_base(g.n_chunks, g.total_len, with_index);
+    const uint32_t ppc = paged_pages_per_chunk(g.chunk_size);
+    const uint64_t dir_entry = 16ull * (ppc + 1u);
+    JoinSources src{};
+    TrailerRuns trailers{};
+    Profiler prof(c, s);
+    hipError_t e = hipMemsetAsync(d_err, 0, sizeof(uint32_t), s);
+    uint32_t live = 0;
+    uint64_t K = 0, index_at = index_base(g.n_chunks);
+    for (uint32_t i = 0; i < n_parts; ++i) {
+        const density_hip_join_part_t& q = parts[i];
+        if (q.chunk_count == 0) continue;
+        const density_hip_header_t& h = *q.header;
+        const uint8_t* d_in = (const uint8_t*)q.container;
+        const bool paged = h.flags & DENSITY_HIP_FLAG_PAGED;
+        const uint64_t stride = (h.flags & DENSITY_HIP_FLAG_SLOTTED) ? slot_stride(h.algo, h.chunk_size) : 0;
+        const uint64_t pbase = payload_base(h.n_chunks, h.total_len, with_index);          // (paged: the directory's base)
+        const size_t body_len = h.container_len - header_trailer(h), len = slice_len(h, q.first_chunk, q.chunk_count);
+        src.p[live] = JoinSource{d_in, body_len, h.total_len, pbase, paged ? kJoinPaged : stride, q.first_chunk, q.chunk_count};
+        trailers.p[live] = TrailerRun{d_in + body_len + 4ull * q.first_chunk, (uint32_t)K, q.chunk_count};
+        if (paged && e == hipSuccess) {
+            const uint64_t pages_base = paged_pages_base(h.n_chunks, h.total_len, h.chunk_size);
+            e = launch_check_directory(d_in + 4ull * q.first_chunk, q.chunk_count, h.chunk_size, h.total_len - (uint64_t)q.first_chunk * h.chunk_size,
+                                       pbase + (dir_entry - 4ull) * q.first_chunk, ppc, (uint32_t)((body_len - pages_base) / kPageBytes), d_lens + K, d_err, s);
+        }
+        if (with_index) {                                                                  // (every part but the last covers whole chunks: whole index bytes)
+            if (e == hipSuccess) e = hipMemcpyAsync(d_out + index_at, d_in + index_base(h.n_chunks) + (uint64_t)q.first_chunk * h.chunk_size / 256, index_bytes(len, true), hipMemcpyDeviceToDevice, s);
+            index_at += index_bytes(len, true);
+        }
+        K += q.chunk_count;
+        ++live;
+    }
+    if (e == hipSuccess) e = launch_join_layout(src, live, (uint32_t)g.algo, g.chunk_size, d_out, cap, out_h, out_base, d_lens, d_src, d_dst_off, d_err, s);
+    prof.mark("join_layout");
+    if (e == hipSuccess) e = launch_join_gather(d_src, d_lens, d_dst_off, (uint32_t)g.n_chunks, safe_size(g.algo, g.chunk_size), d_out, d_err, s);
+    K = 0;
+    for (uint32_t i = 0; i < n_parts; ++i) {
+        const density_hip_join_part_t& q = parts[i];
+        if (q.chunk_count == 0) continue;
+        const density_hip_header_t& h = *q.header;
+        if ((h.flags & DENSITY_HIP_FLAG_PAGED) && e == hipSuccess)
+            e = launch_unpage((const uint8_t*)q.container, q.chunk_count, payload_base(h.n_chunks, h.total_len, with_index) + dir_entry * q.first_chunk,
+                              paged_pages_base(h.n_chunks, h.total_len, h.chunk_size), ppc, d_lens + K, d_dst_off + K, d_out, d_err, s);
+        K += q.chunk_count;
+    }
+    prof.mark("join_gather");
+    if (sealed) {
+        if (e == hipSuccess) e = launch_join_trailers(trailers, live, d_out, cap, (uint32_t)g.n_chunks, d_err, s);
+        prof.mark("move_trailer");
+    }
+    if (e != hipSuccess) { set_error("kernel launch (join)", e); return DENSITY_HIP_ERR_RUNTIME; }
+    if (header_out) {
+        uint32_t h_err = 0;
+        e = read_back(s, d_err, &h_err, header_out, d_out, sizeof(*header_out));
+        if (e != hipSuccess) { set_error("join (device)", e); return DENSITY_HIP_ERR_RUNTIME; }
+        if (h_err & 4u) { set_error("join: a window the call cannot follow (size table, slots or page directory of its chunks)"); return DENSITY_HIP_ERR_FORMAT; }
+        if (h_err) { set_error("container does not fit the output capacity"); return DENSITY_HIP_ERR_CAPACITY; }
+    }
+    return DENSITY_HIP_OK;
+}
+
 // The seal of the container just written for d_in, in place: every chunk of the INPUT summed (checksum.hip), the trailer behind the container, the flag
 // and the new length in its header.  Where the container ends, and how the input was cut, is read from the header on the device, so that nothing here
 // waits for the encoder; the caller's copy of the header only lets the call refuse at once what the device would refuse.
@@ -714,6 +827,38 @@ int density_hip_slice_device(const void* d_container, size_t container_size, con
     uint8_t* ws = nullptr;
     if (const int rc = resolve_workspace(c, d_workspace, workspace_size, need, need, &ws)) return rc;
     return run_slice_container(c, (const uint8_t*)d_container, h, first_chunk, chunk_count, (uint8_t*)d_output, output_capacity, ws, s, header_out);
+}
+
+size_t density_hip_join_bound(const density_hip_join_part_t* parts, uint32_t n_parts) {
+    JoinGeometry g;
+    return join_geometry(parts, n_parts, &g) ? 0 : join_bound(g);
+}
+
+size_t density_hip_join_workspace_size(uint32_t n_parts, uint32_t n_chunks_out) {
+    return (n_parts == 0 || n_parts > DENSITY_HIP_JOIN_MAX_PARTS || n_chunks_out == 0) ? 0 : plan_join(n_chunks_out).total;
+}
+
+int density_hip_join_device(const density_hip_join_part_t* parts, uint32_t n_parts, void* d_output, size_t output_capacity, void* d_workspace, size_t workspace_size,
+                            void* stream, density_hip_header_t* header_out) {
+    g_last_error.clear();
+    JoinGeometry g;
+    if (const char* why = join_geometry(parts, n_parts, &g)) { set_error(why); return DENSITY_HIP_ERR_ARGUMENT; }
+    if (!d_output) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
+    const uintptr_t o0 = (uintptr_t)d_output, o1 = o0 + output_capacity;
+    for (uint32_t p = 0; p < n_parts; ++p) {
+        const uintptr_t c0 = (uintptr_t)parts[p].container, c1 = c0 + parts[p].container_size;
+        if (parts[p].chunk_count && c0 < o1 && o0 < c1) { set_error("join: the output overlaps a part"); return DENSITY_HIP_ERR_ARGUMENT; }
+    }
+    if (output_capacity < join_bound(g)) { set_error("output capacity below density_hip_join_bound()"); return DENSITY_HIP_ERR_CAPACITY; }
+    if (const int rc = check_join_parts(parts, n_parts)) return rc;
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return DENSITY_HIP_ERR_RUNTIME;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const size_t need = plan_join(g.n_chunks).total;
+    uint8_t* ws = nullptr;
+    if (const int rc = resolve_workspace(c, d_workspace, workspace_size, need, need, &ws)) return rc;
+    return run_join_container(c, parts, n_parts, g, (uint8_t*)d_output, output_capacity, ws, s, header_out);
 }
 
 int density_hip_decode_device(const void* d_container, size_t container_size, const density_hip_header_t* header, void* d_output,

@@ -377,6 +377,40 @@ size_t density_hip_slice(const uint8_t* container, size_t container_size, uint32
     return (size_t)out_h.container_len;
 }
 
+size_t density_hip_join(const density_hip_join_part_t* parts, uint32_t n_parts, uint8_t* output, size_t output_size) {
+    g_last_error.clear();
+    JoinGeometry g;
+    if (const char* why = join_geometry(parts, n_parts, &g)) { set_error(why); return 0; }
+    if (!output) { set_error("bad argument"); return 0; }
+    const size_t bound = join_bound(g);
+    if (output_size < bound) { set_error("output capacity below density_hip_join_bound()"); return 0; }
+    if (check_join_parts(parts, n_parts) != DENSITY_HIP_OK) return 0;
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    // staged whole, like every sealed container: the parts' containers up, one behind the other, the joined container down
+    density_hip_join_part_t staged[DENSITY_HIP_JOIN_MAX_PARTS];
+    size_t in_bytes = 0;
+    for (uint32_t p = 0; p < n_parts; ++p) {
+        staged[p] = parts[p];
+        if (parts[p].chunk_count == 0) continue;
+        staged[p].container = (const void*)in_bytes;                                     // (the offset for now: the buffer may still move)
+        in_bytes += align_up(parts[p].header->container_len, kAlign);
+    }
+    hipError_t e = ensure_staging(c, in_bytes, bound, plan_join(g.n_chunks).total);
+    for (uint32_t p = 0; p < n_parts && e == hipSuccess; ++p) {
+        if (parts[p].chunk_count == 0) continue;
+        staged[p].container = (const uint8_t*)c->stage_in.p + (size_t)staged[p].container;
+        e = copy_host_side_pinned(const_cast<void*>(staged[p].container), parts[p].container, parts[p].header->container_len, hipMemcpyHostToDevice, c->stream);
+    }
+    if (e != hipSuccess) { set_error("staging (H2D)", e); return 0; }
+    density_hip_header_t out_h;
+    if (run_join_container(c, staged, n_parts, g, (uint8_t*)c->stage_out.p, bound, (uint8_t*)c->work.p, c->stream, &out_h) != DENSITY_HIP_OK) return 0;
+    e = copy_host_side_pinned(output, c->stage_out.p, out_h.container_len, hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) { set_error("staging (D2H)", e); return 0; }
+    return (size_t)out_h.container_len;
+}
+
 size_t density_hip_parity(const uint8_t* input, size_t input_size, size_t chunk_size, uint32_t n_groups, uint8_t* parity, size_t parity_capacity) {
     return parity_staged(1, input, input_size, chunk_size, n_groups, parity, parity_capacity);
 }

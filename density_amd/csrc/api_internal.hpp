@@ -391,6 +391,25 @@ int run_seal_container(DeviceCtx* c, const uint8_t* d_in, size_t n, uint8_t* d_o
 // chunks [first, first + count) of the container at d_in (header h: checked, the window inside it, cap >= slice_bound()) as a packed container at d_out
 int run_slice_container(DeviceCtx* c, const uint8_t* d_in, const density_hip_header_t& h, uint32_t first, uint32_t count, uint8_t* d_out, size_t cap, uint8_t* ws,
                         hipStream_t s, density_hip_header_t* header_out);
+// a join (density_hip_join_device): what its part list comes to — algorithm, chunk size and the flags the parts share, the output's chunks and input bytes, the
+// parts that are not skipped — or why it is refused; the capacity it asks for; every live part's header against its container_size (DENSITY_HIP_ERR_FORMAT)
+struct JoinGeometry { int algo; uint32_t chunk_size, flags, live; uint64_t n_chunks, total_len; };
+const char* join_geometry(const density_hip_join_part_t* parts, uint32_t n_parts, JoinGeometry* g);
+size_t join_bound(const JoinGeometry& g);
+int check_join_parts(const density_hip_join_part_t* parts, uint32_t n_parts);
+// the scratch of a join in a workspace: the error word and the run table, three words per output chunk (the part table travels with the launches
+// and takes no room here)
+struct JoinPlan {
+    size_t n_chunks, total;
+    uint32_t* err(uint8_t* ws) const { return reinterpret_cast<uint32_t*>(ws); }
+    uint64_t* lens(uint8_t* ws) const { return reinterpret_cast<uint64_t*>(ws + kAlign); }
+    uint64_t* src(uint8_t* ws) const { return lens(ws) + align_up(n_chunks, kAlign / 8); }
+    uint64_t* dst_off(uint8_t* ws) const { return src(ws) + align_up(n_chunks, kAlign / 8); }
+};
+inline JoinPlan plan_join(size_t n_chunks) { return JoinPlan{n_chunks, kAlign + 3 * align_up(8 * n_chunks, kAlign)}; }
+// the parts' windows (device pointers; join_geometry and check_join_parts passed, cap >= join_bound()) as one packed container at d_out; `ws`: plan_join().total bytes
+int run_join_container(DeviceCtx* c, const density_hip_join_part_t* parts, uint32_t n_parts, const JoinGeometry& g, uint8_t* d_out, size_t cap, uint8_t* ws,
+                       hipStream_t s, density_hip_header_t* header_out);
 // ... of one reference stream (api_stream.hip)
 int run_stream_encode(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, uint8_t* ws, hipStream_t s, size_t* size_out);
 int run_stream_decode(DeviceCtx* c, int algo, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, uint8_t* ws, hipStream_t s, size_t* size_out);

@@ -150,6 +150,28 @@ __global__ __launch_bounds__(kSmallThreads) void move_trailer_kernel(const uint8
     }
 }
 
+// The trailer of a joined container: n_parts runs of trailer words, run p to entries [entry, entry + count) of the n-word trailer behind the packed container
+// the join's layout and gather have just written into `dst`; the gap in front and the padding once, as move_trailer_kernel writes them.
+__global__ __launch_bounds__(kSmallThreads) void join_trailers_kernel(TrailerRuns runs, uint32_t n_parts, uint8_t* __restrict__ dst, uint64_t capacity, uint32_t n,
+                                                                      uint32_t* __restrict__ err) {
+    if (*err) return;
+    const uint64_t len = ld64u(dst + 24), at = align16(len), bytes = align16(4ull * n);
+    const uint32_t flags = ld16u(dst + 6);
+    if (at + bytes > capacity) { if (threadIdx.x == 0) atomicOr(err, 2u); return; }
+    __syncthreads();
+    for (uint32_t p = 0; p < n_parts; ++p) {
+        const TrailerRun r = runs.p[p];
+        if ((uint64_t)r.entry + r.count > n) continue;                       // (never from this library's host side)
+        for (uint32_t i = threadIdx.x; i < r.count; i += kSmallThreads) st32u(dst + at + 4ull * (r.entry + i), ld32u(r.src + 4ull * i));
+    }
+    if (threadIdx.x < at - len) dst[len + threadIdx.x] = 0;
+    if (threadIdx.x < bytes - 4ull * n) dst[at + 4ull * n + threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+        st16u(dst + 6, flags | DENSITY_HIP_FLAG_CHECKSUM);
+        st64u(dst + 24, at + bytes);
+    }
+}
+
 hipError_t launch_tiles(const uint8_t* d_data, uint64_t size, uint32_t chunk, uint32_t n_chunks, const uint32_t* d_geom, uint32_t* d_acc, hipStream_t stream) {
     // with the geometry on the device alone, the tiles of the input as a whole stand in for the tiles of its chunks: the loop takes the rest
     const uint64_t units = d_geom ? (size + kSumTile - 1) / kSumTile : (uint64_t)n_chunks * ((chunk + kSumTile - 1) / kSumTile);
@@ -198,6 +220,12 @@ hipError_t launch_seal(const uint8_t* d_in, uint64_t input_size, uint8_t* d_cont
 
 hipError_t launch_move_trailer(const uint8_t* d_trailer, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err, hipStream_t stream) {
     hipLaunchKernelGGL(move_trailer_kernel, dim3(1), dim3(kSmallThreads), 0, stream, d_trailer, d_container, capacity, n_chunks, d_err);
+    return hipGetLastError();
+}
+
+hipError_t launch_join_trailers(const TrailerRuns& runs, uint32_t n_parts, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err,
+                                hipStream_t stream) {
+    hipLaunchKernelGGL(join_trailers_kernel, dim3(1), dim3(kSmallThreads), 0, stream, runs, n_parts, d_container, capacity, n_chunks, d_err);
     return hipGetLastError();
 }
 

@@ -389,6 +389,116 @@ __global__ __launch_bounds__(kCopyThreads) void slice_gather_kernel(const uint8_
     }
 }
 
+// ---- chunk windows of several containers -> one packed container (density_hip_join_device) ----
+// The joined layout, one work-group.  The parts are walked in order; per part the scan is slice_layout_kernel's (a packed source's size table from chunk 0 on,
+// with the tile carry, for the window's source offset; the other forms from chunk `first`), and a second carry runs across the parts: K, the output's chunk
+// number of the part's first chunk, and `at`, the offset in `out` where its first stream goes — the 16-byte boundary behind the part in front.  Per output
+// chunk for the gather: lens, src (the stream's address, 0 for a paged part's chunk: unpage_kernel moves those) and dst_off.  One run per CHUNK, of the
+// stream's bytes alone: what stands behind a source's stream is its own gap, another part's business, the trailer's padding or nothing at all, so every gap
+// of the output — behind each stream but the last, the parts' seams included — is written here.  Refusals are slice_layout_kernel's, judged inside the
+// windows only: bit 4 of *err, and then no gap is written and container_len says out_base.
+__global__ __launch_bounds__(kScanThreads) void join_layout_kernel(JoinSources parts, uint32_t n_parts, uint32_t algo, uint64_t chunk_bytes, uint8_t* __restrict__ out,
+                                                                   uint64_t capacity, density_hip_header_t hdr, uint64_t out_base, uint64_t* lens,
+                                                                   uint64_t* __restrict__ src, uint64_t* dst_off, uint32_t* __restrict__ err) {
+    __shared__ uint64_t wave_sums[kScanThreads / 64];
+    __shared__ uint64_t s_first, s_end;
+    __shared__ uint32_t s_bad;
+    if (threadIdx.x == 0) { s_first = 0; s_end = 0; s_bad = *err; }                              // (paged parts: what the directory checks raised)
+    __syncthreads();
+    uint64_t K = 0, at = out_base, end = out_base;
+    for (uint32_t p = 0; p < n_parts; ++p) {
+        const JoinSource& part = parts.p[p];
+        const uint8_t* in = part.in;
+        const bool paged = part.slot_stride == kJoinPaged;
+        const uint64_t slot_stride = paged ? 0ull : part.slot_stride, limit = part.limit, total_len = part.total_len, src_base = part.src_base;
+        const uint64_t first = part.first, count = part.count;
+        const uint64_t from = (slot_stride || paged) ? first : 0u, to = first + count;
+        uint64_t carry = 0;
+        for (uint64_t t0 = from; t0 < to; t0 += kScanThreads) {
+            const uint64_t i = t0 + threadIdx.x;
+            const bool in_window = i >= first && i < to;
+            uint64_t raw = 0, keep = 0;
+            if (i < to) {
+                keep = raw = ld32u(in + kHeaderBytes + 4ull * i);
+                if (in_window) {
+                    const uint64_t a = i * chunk_bytes, len = total_len - a < chunk_bytes ? total_len - a : chunk_bytes;
+                    if (paged) keep = lens[K + (i - first)];
+                    else if (raw > safe_size_of(algo, len) || (slot_stride && raw > slot_stride)) { keep = 0; atomicOr(&s_bad, 4u); }
+                }
+            }
+            uint64_t tile_total = 0;
+            const uint64_t excl = carry + block_inclusive_scan(align16(keep), wave_sums, &tile_total) - align16(keep);
+            if (in_window) {
+                const uint64_t k = K + (i - first);
+                const uint64_t so = paged ? 0ull : slot_stride ? src_base + i * slot_stride : src_base + excl;
+                if (!paged && (so > limit || keep > limit - so)) { keep = 0; atomicOr(&s_bad, 4u); }  // the stream runs past its container: the gather must not follow it
+                src[k] = paged ? 0ull : (uint64_t)(uintptr_t)(in + so);
+                dst_off[k] = excl;                                                               // (from the scan's start: made the output's below)
+                if (!paged) lens[k] = keep;
+                st32u(out + kHeaderBytes + 4ull * k, (uint32_t)raw);
+                if (i == first) s_first = excl;
+                if (i == to - 1) s_end = excl + keep;
+            }
+            carry += tile_total;
+        }
+        __syncthreads();
+        const uint64_t first_at = s_first, span = s_end - first_at;
+        for (uint64_t k = threadIdx.x; k < count; k += kScanThreads) dst_off[K + k] = at + (dst_off[K + k] - first_at);
+        end = at + span;
+        at = align16(end);
+        K += count;
+        __syncthreads();                                                                         // (s_first and s_end are the next part's now)
+    }
+    const bool bad = s_bad != 0 || end > capacity;
+    for (uint64_t k = threadIdx.x; k < K; k += kScanThreads) {
+        const uint64_t e = dst_off[k] + lens[k];
+        if (!bad && k + 1 < K) for (uint64_t q = e; q < align16(e); ++q) out[q] = 0;             // the gap behind the stream is part of the container: zeros
+    }
+    if (threadIdx.x == 0) {
+        if (bad) atomicOr(err, s_bad ? 4u : 2u);
+        const uint64_t len = bad ? out_base : end;
+        st32u(out, hdr.magic);
+        st32u(out + 4, (uint32_t)hdr.algo | (uint32_t)hdr.version << 8 | (uint32_t)hdr.flags << 16);
+        st32u(out + 8, hdr.chunk_size);
+        st32u(out + 12, hdr.n_chunks);
+        st32u(out + 16, (uint32_t)hdr.total_len);
+        st32u(out + 20, (uint32_t)(hdr.total_len >> 32));
+        st32u(out + 24, (uint32_t)len);
+        st32u(out + 28, (uint32_t)(len >> 32));
+    }
+    // (as in layout_encode_kernel: the gaps in front of the payloads are zeros)
+    const uint64_t table_end = kHeaderBytes + 4ull * hdr.n_chunks, ibase = (table_end + 15) / 16 * 16;
+    const uint64_t iend = ibase + ((hdr.flags & DENSITY_HIP_FLAG_BLOCK_INDEX) ? (hdr.total_len + 255) / 256 : 0);
+    if (threadIdx.x < ibase - table_end) out[table_end + threadIdx.x] = 0;
+    if (threadIdx.x >= 32 && threadIdx.x - 32 < out_base - iend) out[iend + threadIdx.x - 32] = 0;
+}
+
+// The join's gather: slice_gather_kernel's tiles and cut — bytes up to the DESTINATION's first 16-byte boundary, aligned 16-byte stores fed from loads at
+// whatever phase that gives the source, the tail bytes — with the run's source an address of its own, because the parts lie in different allocations.  A run
+// is one output chunk's stream (tiles_per_run covers the longest a stream can be; the tiles behind a run's end leave at once), so the work follows the bytes
+// moved and no run carries a gap.  src[r] == 0: a paged part's chunk, not moved here.  Nothing where *err is set.
+__global__ __launch_bounds__(kCopyThreads) void join_gather_kernel(const uint64_t* __restrict__ src, const uint64_t* __restrict__ lens, const uint64_t* __restrict__ dst_off,
+                                                                   uint32_t runs, uint64_t tiles_per_run, uint8_t* __restrict__ out, const uint32_t* __restrict__ err) {
+    if (*err) return;
+    const uint64_t units = (uint64_t)runs * tiles_per_run;
+    for (uint64_t u = blockIdx.x; u < units; u += gridDim.x) {
+        const uint64_t r = u / tiles_per_run, t0 = (u % tiles_per_run) * kCopyTile, len = lens[r], from = src[r];
+        if (t0 >= len || from == 0) continue;
+        const uint32_t n = len - t0 < kCopyTile ? (uint32_t)(len - t0) : kCopyTile;
+        const uint8_t* s = reinterpret_cast<const uint8_t*>((uintptr_t)from) + t0;
+        uint8_t* d = out + dst_off[r] + t0;
+        const uint32_t lead = (0u - (uint32_t)(uintptr_t)d) & 15u, head = lead < n ? lead : n;
+        const uint32_t full = (n - head) / 16u, tail_at = head + 16u * full;                     // (full <= 1024: four stores a lane cover it)
+        u32x4 v[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) { const uint32_t i = j * kCopyThreads + threadIdx.x; if (i < full) v[j] = *reinterpret_cast<const u32x4_u*>(s + head + 16ull * i); }
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) { const uint32_t i = j * kCopyThreads + threadIdx.x; if (i < full) *reinterpret_cast<u32x4*>(d + head + 16ull * i) = v[j]; }
+        if (threadIdx.x < head) d[threadIdx.x] = s[threadIdx.x];
+        if (threadIdx.x < n - tail_at) d[tail_at + threadIdx.x] = s[tail_at + threadIdx.x];
+    }
+}
+
 // LDS ordering assumptions of chameleon.hip, checked on the device the library is running on.
 __global__ __launch_bounds__(64) void selftest_kernel(uint32_t* __restrict__ fail) {
     __shared__ __attribute__((aligned(16))) uint16_t cells[256];
@@ -508,6 +618,22 @@ hipError_t launch_slice_gather(const uint8_t* d_container, const uint64_t* d_src
     if (units == 0) return hipSuccess;
     hipLaunchKernelGGL(slice_gather_kernel, dim3((uint32_t)(units < kSliceMaxGroups ? units : kSliceMaxGroups)), dim3(kCopyThreads), 0, stream, d_container, d_src_off,
                        d_lens, d_dst_off, runs, tiles, d_out, d_err);
+    return hipGetLastError();
+}
+
+hipError_t launch_join_layout(const JoinSources& parts, uint32_t n_parts, uint32_t algo, uint64_t chunk_bytes, uint8_t* d_out, uint64_t capacity,
+                              density_hip_header_t hdr, uint64_t out_base, uint64_t* d_lens, uint64_t* d_src, uint64_t* d_dst_off, uint32_t* d_err, hipStream_t stream) {
+    hipLaunchKernelGGL(join_layout_kernel, dim3(1), dim3(kScanThreads), 0, stream, parts, n_parts, algo, chunk_bytes, d_out, capacity, hdr, out_base, d_lens, d_src,
+                       d_dst_off, d_err);
+    return hipGetLastError();
+}
+
+hipError_t launch_join_gather(const uint64_t* d_src, const uint64_t* d_lens, const uint64_t* d_dst_off, uint32_t runs, uint64_t longest_run, uint8_t* d_out,
+                              const uint32_t* d_err, hipStream_t stream) {
+    const uint64_t tiles = (longest_run + kCopyTile - 1) / kCopyTile, units = tiles * runs;
+    if (units == 0) return hipSuccess;
+    hipLaunchKernelGGL(join_gather_kernel, dim3((uint32_t)(units < kSliceMaxGroups ? units : kSliceMaxGroups)), dim3(kCopyThreads), 0, stream, d_src, d_lens, d_dst_off,
+                       runs, tiles, d_out, d_err);
     return hipGetLastError();
 }
 

@@ -254,3 +254,32 @@ def decode_multi_device(blob, out, salvage=False):
                 raise container.DecodeError(f"rank {rank}: decoded {got} bytes where the row says {nb}")
         at += nb
     return damaged_rows if salvage else at
+
+
+def multi_to_container_device(blob, out=None):
+    """A device-resident super-container "DHCM" as ONE DHC1 container on the same device: the join of its rows (density_hip_join_device), whatever form each
+    row's container has — paged, slotted or packed; all sealed or none — with empty rows skipped.  Every shard but the last non-empty one covers whole chunks
+    (shard_chunks), which is what the join asks for.  `out`: a contiguous uint8 tensor on blob's device of at least container.join_bound() bytes, or None for
+    one made here.  Returns the view of `out` that holds the container: for shards this library encoded, byte for byte what encode_device (+ seal_device)
+    writes for the whole input.  Runs on torch's current stream."""
+    from . import container
+    hdr, rows = parse_multi(blob)
+    src = blob if blob.is_contiguous() else blob.contiguous()
+    parts = []
+    for off, ln, nb in rows:
+        if nb == 0 or ln < HEADER_BYTES:
+            continue
+        h = container.parse_header(bytes(src[off:off + HEADER_BYTES].cpu().numpy()))
+        parts.append((src.data_ptr() + off, ln, h, 0, h.n_chunks))
+    cap = container.join_bound(parts)
+    if cap == 0:
+        raise ValueError("the rows of this DHCM container do not join (no chunks, or rows that differ in algorithm, chunk size, block index or seal)")
+    if out is None:
+        out = torch.empty(cap, dtype=torch.uint8, device=blob.device)
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != blob.device or out.numel() < cap:
+        raise ValueError(f"out must be a contiguous uint8 tensor on {blob.device} of at least {cap} bytes")
+    with torch.cuda.device(blob.device):
+        joined = container.join_device(parts, out.data_ptr(), out.numel(), stream=torch.cuda.current_stream().cuda_stream)
+    if joined.total_len != hdr["total_len"]:
+        raise ValueError(f"the rows hold {joined.total_len} input bytes where the DHCM header says {hdr['total_len']}")
+    return out[:joined.container_len]

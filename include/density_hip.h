@@ -272,6 +272,54 @@ size_t density_hip_slice_bound(const density_hip_header_t* header, uint32_t firs
 int density_hip_slice_device(const void* d_container, size_t container_size, const density_hip_header_t* header, uint32_t first_chunk, uint32_t chunk_count,
                              void* d_output, size_t output_capacity, void* d_workspace, size_t workspace_size, void* stream, density_hip_header_t* header_out);
 size_t density_hip_slice(const uint8_t* container, size_t container_size, uint32_t first_chunk, uint32_t chunk_count, uint8_t* output, size_t output_size);
+/* Join: chunk windows of several containers as ONE packed container — the slice's inverse.  Append is a join of two whole containers; replacing chunk k of A
+ * by the one-chunk container B is join(A[0, k), B, A[k + 1, n)); a multi-rank container "DHCM" becomes a "DHC1" by joining its rows.  A part is
+ * a window [first_chunk, first_chunk + chunk_count) of a packed, slotted or PAGED container, sealed or not; forms may differ from part to part.  No stream is
+ * parsed or re-encoded: one pass over the encoded bytes.  The output is an ordinary PACKED container: magic, algo, version and chunk_size those of the parts,
+ * n_chunks = N = the sum of the windows' counts, total_len = L = the sum of the windows' decoded lengths (a window's length as the slice defines it), flags = the
+ * parts' common DENSITY_HIP_FLAG_BLOCK_INDEX and DENSITY_HIP_FLAG_CHECKSUM and nothing else; behind the header the windows' size-table entries in order, the
+ * windows' block-index bytes concatenated, every stream at the next 16-byte boundary behind the one before with zeros in the gaps (the gap between the last
+ * stream of one part and the first of the next too), container_len where the last stream ends, and for sealed parts, behind round_up(E, 16), the windows'
+ * trailer entries concatenated and zero-padded.  Every byte up to container_len is written, none at or beyond it.  For containers this library made: byte for
+ * byte what density_hip_encode_device() (+ density_hip_seal_device()) writes for the concatenation of the windows' inputs with the same chunk_size.  Every call
+ * that takes a container takes the result.  All buffers at ANY byte alignment.
+ *   A part: `container` a device pointer (density_hip_join_device) or a host pointer (density_hip_join); `header` a HOST copy of the part's first 32 bytes,
+ *     REQUIRED — the output's geometry is host arithmetic; chunk_count == 0: the part is skipped and nothing of it is read, not even its pointers.
+ *   - DENSITY_HIP_ERR_ARGUMENT on the host, nothing written, no device work: n_parts == 0 or above DENSITY_HIP_JOIN_MAX_PARTS, or N == 0; a part (not skipped) with
+ *     a NULL pointer, a NULL header or a container_size below a header's 32 bytes; a header that is not a container's; a window outside its container's chunks; parts that differ in algo, chunk_size, the
+ *     BLOCK_INDEX flag or the CHECKSUM flag; a part other than the last (of those not skipped) whose window's length is not chunk_count * chunk_size — a ragged
+ *     chunk may only be the output's last, and block-index slices then concatenate without re-basing; N above 2^32 - 1; an output range that overlaps a part's
+ *     range (the device call).
+ *   - output_capacity < density_hip_join_bound(): DENSITY_HIP_ERR_CAPACITY at once, nothing written.
+ *   - a part whose header or trailer does not fit its container_size: DENSITY_HIP_ERR_FORMAT at once, nothing written.
+ *   - DENSITY_HIP_ERR_FORMAT found on the device, by the layout kernel in front of the gather, and then no payload byte is written for ANY part: the slice's faults,
+ *     per part, judged in each part's window only — an entry above its chunk's worst case or its slot, a stream that runs past its container, for a PAGED part every
+ *     fault density_hip_unpage_device knows.  Damage outside the windows is not this call's business; the slice's one exception holds per packed part: a lying
+ *     entry in front of a packed window moves that window.
+ *   density_hip_join_bound: density_hip_container_bound(algo, L, chunk_size), plus density_hip_seal_overhead(L, chunk_size) for sealed parts; 0 for anything the
+ *     ARGUMENT list above refuses on the host.  Pure host arithmetic: no device, no HIP call.
+ *   density_hip_join_workspace_size: what a caller's workspace must hold for n_parts parts (1 .. DENSITY_HIP_JOIN_MAX_PARTS, skipped ones need not count) and N
+ *     output chunks; 0 outside that.  Pure host arithmetic.  d_workspace == NULL: the library's cached per-device workspace, which, like a caller's, must overlap
+ *     neither the parts nor the output.
+ *   - header_out == NULL: fully asynchronous — the part table and the headers it points to are read before the call returns, nothing is reported (refused windows
+ *     leave the payloads unwritten), nothing about the sources crosses back to the host.  With header_out the call synchronises, returns the joined header and
+ *     reports DENSITY_HIP_ERR_FORMAT / _CAPACITY.
+ *   density_hip_join: the host-pointer form, staged whole; returns the bytes written, 0 on failure with density_hip_last_error() set.
+ * Profiling marks: "join_layout", "join_gather" and, for sealed parts, "move_trailer".
+ * Out of scope: parity blobs "DHP1" (a blob's rows span its whole input: the joined input wants a blob of its own, density_hip_parity_device); parts whose chunk
+ * sizes differ, and re-chunking; a ragged chunk anywhere but at the end; in-place joins, where the output overlaps a part. */
+#define DENSITY_HIP_JOIN_MAX_PARTS 64u
+typedef struct density_hip_join_part {
+    const void* container;
+    size_t container_size;
+    const density_hip_header_t* header;
+    uint32_t first_chunk, chunk_count;
+} density_hip_join_part_t;
+size_t density_hip_join_bound(const density_hip_join_part_t* parts, uint32_t n_parts);
+size_t density_hip_join_workspace_size(uint32_t n_parts, uint32_t n_chunks_out);
+int density_hip_join_device(const density_hip_join_part_t* parts, uint32_t n_parts, void* d_output, size_t output_capacity, void* d_workspace, size_t workspace_size,
+                            void* stream, density_hip_header_t* header_out);
+size_t density_hip_join(const density_hip_join_part_t* parts, uint32_t n_parts, uint8_t* output, size_t output_size);
 /* `header` may be NULL: it is then read back from the device (one small synchronous copy). */
 int density_hip_decode_device(const void* d_container, size_t container_size, const density_hip_header_t* header,
                               void* d_output, size_t output_capacity, void* d_workspace, size_t workspace_size,
