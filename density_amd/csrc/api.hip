@@ -475,53 +475,6 @@ int run_unpage_container(DeviceCtx* c, const uint8_t* d_in, const density_hip_he
     return DENSITY_HIP_OK;
 }
 
-// chunks [first, first + count) of a container of any form -> a packed container: the window's size-table entries, index bytes and trailer entries lie where the
-// host can say; where its streams lie the layout kernel finds out on the device and leaves there for the gather
-int run_slice_container(DeviceCtx* c, const uint8_t* d_in, const density_hip_header_t& h, uint32_t first, uint32_t count, uint8_t* d_out, size_t cap, uint8_t* ws,
-                        hipStream_t s, density_hip_header_t* header_out) {
-    const DecodePlan p = plan_decode(h.algo, h.n_chunks);
-    uint32_t* d_err = p.err(ws);
-    uint64_t *d_dst_off = p.sizes(ws), *d_src_off = p.offsets(ws), *d_run = p.offsets(ws) + h.n_chunks, *d_lens = p.produced(ws);
-    const bool with_index = h.flags & DENSITY_HIP_FLAG_BLOCK_INDEX, paged = h.flags & DENSITY_HIP_FLAG_PAGED;
-    const uint64_t stride = (h.flags & DENSITY_HIP_FLAG_SLOTTED) ? slot_stride(h.algo, h.chunk_size) : 0;
-    const uint64_t pbase = payload_base(h.n_chunks, h.total_len, with_index);          // (paged: the directory's base)
-    const size_t trailer = header_trailer(h), body_len = h.container_len - trailer;    // the streams and pages end in front of a sealed container's trailer
-    const size_t len = slice_len(h, first, count);
-    const density_hip_header_t out_h = make_header(h.algo, h.chunk_size, count, len, h.flags & DENSITY_HIP_FLAG_BLOCK_INDEX);
-    const uint64_t out_base = payload_base(count, len, with_index);
-    Profiler prof(c, s);
-    hipError_t e = hipMemsetAsync(d_err, 0, sizeof(uint32_t), s);
-    const uint64_t dir_entry = 16ull * (paged_pages_per_chunk(h.chunk_size) + 1u), pages_base = paged ? paged_pages_base(h.n_chunks, h.total_len, h.chunk_size) : 0;
-    if (paged) {
-        // the directory check on the window's chunks alone: its chunk 0 is chunk `first` — the size table is read at d_in + 4 * first, the directory so
-        // much further on — and the input ends where the container's does
-        if (e == hipSuccess) e = launch_check_directory(d_in + 4ull * first, count, h.chunk_size, h.total_len - (uint64_t)first * h.chunk_size, pbase + (dir_entry - 4ull) * first,
-                                                        paged_pages_per_chunk(h.chunk_size), (uint32_t)((body_len - pages_base) / kPageBytes), d_lens, d_err, s);
-    }
-    if (e == hipSuccess) e = launch_slice_layout(d_in, body_len, h, first, count, pbase, stride, paged, d_out, cap, out_h, out_base, d_lens, d_src_off, d_dst_off, d_run, d_err, s);
-    if (e == hipSuccess && with_index) e = hipMemcpyAsync(d_out + index_base(count), d_in + index_base(h.n_chunks) + (uint64_t)first * h.chunk_size / 256, index_bytes(len, true), hipMemcpyDeviceToDevice, s);
-    prof.mark("slice_layout");
-    if (e == hipSuccess) {
-        if (paged) e = launch_unpage(d_in, count, pbase + dir_entry * first, pages_base, paged_pages_per_chunk(h.chunk_size), d_lens, d_dst_off, d_out, d_err, s);
-        else if (stride) e = launch_slice_gather(d_in, d_src_off, d_lens, d_dst_off, count, stride, d_out, d_err, s);
-        else e = launch_slice_gather(d_in, d_src_off, d_run, d_dst_off, 1, body_len - pbase, d_out, d_err, s);   // one run: the window's streams lie as the output wants them
-    }
-    prof.mark("slice_gather");
-    if (trailer) {
-        if (e == hipSuccess) e = launch_move_trailer(d_in + body_len + 4ull * first, d_out, cap, count, d_err, s);
-        prof.mark("move_trailer");
-    }
-    if (e != hipSuccess) { set_error("kernel launch (slice)", e); return DENSITY_HIP_ERR_RUNTIME; }
-    if (header_out) {
-        uint32_t h_err = 0;
-        e = read_back(s, d_err, &h_err, header_out, d_out, sizeof(*header_out));
-        if (e != hipSuccess) { set_error("slice (device)", e); return DENSITY_HIP_ERR_RUNTIME; }
-        if (h_err & 4u) { set_error("slice: a window the call cannot follow (size table, slots or page directory of its chunks)"); return DENSITY_HIP_ERR_FORMAT; }
-        if (h_err) { set_error("container does not fit the output capacity"); return DENSITY_HIP_ERR_CAPACITY; }
-    }
-    return DENSITY_HIP_OK;
-}
-
 // ---- join: chunk windows of several containers as one packed container ----
 
 // what the host can say of a join before any byte moves: nullptr and *g, or why the part list is refused (include/density_hip.h: DENSITY_HIP_ERR_ARGUMENT)
@@ -566,12 +519,20 @@ int check_join_parts(const density_hip_join_part_t* parts, uint32_t n_parts) {
 
 // The parts' windows -> one packed container: everything the host can say of a part — where its size table, index bytes, trailer entries and (slotted) streams
 // lie — goes into the part table, which travels with the launches; where a packed part's window lies the layout kernel finds out and leaves on the device.
-// A paged part goes through the directory check and the unpage gather as a slice does, handed offset pointers and its stretch of the join's run table.
-int run_join_container(DeviceCtx* c, const density_hip_join_part_t* parts, uint32_t n_parts, const JoinGeometry& g, uint8_t* d_out, size_t cap, uint8_t* ws,
+// A paged part goes through the directory check and the unpage gather, handed offset pointers and its stretch of the run table.  What the caller brings
+// (WindowCall): the scratch in its own workspace, its profiling marks and its name in the messages.
+struct WindowCall {
+    uint32_t* err;
+    uint64_t *lens, *src, *dst_off;       // a word per output chunk each
+    uint64_t* run;                         // not null: one word, and a single packed part moves as the one run the layout kernel leaves there (the kernel
+                                           // leaves 0 there for more than one part: then as with null, a run per chunk)
+    uint64_t longest_run;                  // what no stream of a part that is not paged exceeds: sizes the gather's tiles per run
+    const char *layout_mark, *gather_mark, *name;
+};
+static int run_windows(DeviceCtx* c, const density_hip_join_part_t* parts, uint32_t n_parts, const JoinGeometry& g, uint8_t* d_out, size_t cap, const WindowCall& w,
                        hipStream_t s, density_hip_header_t* header_out) {
-    const JoinPlan p = plan_join(g.n_chunks);
-    uint32_t* d_err = p.err(ws);
-    uint64_t *d_lens = p.lens(ws), *d_src = p.src(ws), *d_dst_off = p.dst_off(ws);
+    uint32_t* const d_err = w.err;
+    uint64_t *const d_lens = w.lens, *const d_src = w.src, *const d_dst_off = w.dst_off;
     const bool with_index = g.flags & DENSITY_HIP_FLAG_BLOCK_INDEX, sealed = g.flags & DENSITY_HIP_FLAG_CHECKSUM;
     const density_hip_header_t out_h = make_header(g.algo, g.chunk_size, g.n_chunks, g.total_len, g.flags & DENSITY_HIP_FLAG_BLOCK_INDEX);
     const uint64_t out_base = payload_base(g.n_chunks, g.total_len, with_index);
@@ -582,6 +543,7 @@ int run_join_container(DeviceCtx* c, const density_hip_join_part_t* parts, uint3
     Profiler prof(c, s);
     hipError_t e = hipMemsetAsync(d_err, 0, sizeof(uint32_t), s);
     uint32_t live = 0;
+    bool any_unpaged = false;
     uint64_t K = 0, index_at = index_base(g.n_chunks);
     for (uint32_t i = 0; i < n_parts; ++i) {
         const density_hip_join_part_t& q = parts[i];
@@ -591,24 +553,31 @@ int run_join_container(DeviceCtx* c, const density_hip_join_part_t* parts, uint3
         const bool paged = h.flags & DENSITY_HIP_FLAG_PAGED;
         const uint64_t stride = (h.flags & DENSITY_HIP_FLAG_SLOTTED) ? slot_stride(h.algo, h.chunk_size) : 0;
         const uint64_t pbase = payload_base(h.n_chunks, h.total_len, with_index);          // (paged: the directory's base)
-        const size_t body_len = h.container_len - header_trailer(h), len = slice_len(h, q.first_chunk, q.chunk_count);
+        const size_t body_len = h.container_len - header_trailer(h), len = slice_len(h, q.first_chunk, q.chunk_count);   // the streams and pages end in front of a sealed container's trailer
         src.p[live] = JoinSource{d_in, body_len, h.total_len, pbase, paged ? kJoinPaged : stride, q.first_chunk, q.chunk_count};
         trailers.p[live] = TrailerRun{d_in + body_len + 4ull * q.first_chunk, (uint32_t)K, q.chunk_count};
         if (paged && e == hipSuccess) {
+            // the directory check on the window's chunks alone: its chunk 0 is chunk `first` — the size table is read at d_in + 4 * first, the directory so
+            // much further on — and the input ends where the container's does
             const uint64_t pages_base = paged_pages_base(h.n_chunks, h.total_len, h.chunk_size);
             e = launch_check_directory(d_in + 4ull * q.first_chunk, q.chunk_count, h.chunk_size, h.total_len - (uint64_t)q.first_chunk * h.chunk_size,
                                        pbase + (dir_entry - 4ull) * q.first_chunk, ppc, (uint32_t)((body_len - pages_base) / kPageBytes), d_lens + K, d_err, s);
         }
-        if (with_index) {                                                                  // (every part but the last covers whole chunks: whole index bytes)
+        if (with_index) {                                                                  // (chunks are whole blocks, and every part but the last covers whole chunks: whole index bytes)
             if (e == hipSuccess) e = hipMemcpyAsync(d_out + index_at, d_in + index_base(h.n_chunks) + (uint64_t)q.first_chunk * h.chunk_size / 256, index_bytes(len, true), hipMemcpyDeviceToDevice, s);
             index_at += index_bytes(len, true);
         }
+        any_unpaged |= !paged;
         K += q.chunk_count;
         ++live;
     }
-    if (e == hipSuccess) e = launch_join_layout(src, live, (uint32_t)g.algo, g.chunk_size, d_out, cap, out_h, out_base, d_lens, d_src, d_dst_off, d_err, s);
-    prof.mark("join_layout");
-    if (e == hipSuccess) e = launch_join_gather(d_src, d_lens, d_dst_off, (uint32_t)g.n_chunks, safe_size(g.algo, g.chunk_size), d_out, d_err, s);
+    if (e == hipSuccess) e = launch_window_layout(src, live, (uint32_t)g.algo, g.chunk_size, d_out, cap, out_h, out_base, d_lens, d_src, d_dst_off, w.run, d_err, s);
+    prof.mark(w.layout_mark);
+    if (e == hipSuccess) {
+        // one packed part of a caller that asked for it: ONE run, its streams lie as the output wants them, gaps included; else a run per chunk (none of a paged part's)
+        if (w.run && live == 1 && src.p[0].slot_stride == 0) e = launch_run_gather(d_src, w.run, d_dst_off, 1, src.p[0].limit - src.p[0].src_base, d_out, d_err, s);
+        else if (any_unpaged) e = launch_run_gather(d_src, d_lens, d_dst_off, (uint32_t)g.n_chunks, w.longest_run, d_out, d_err, s);
+    }
     K = 0;
     for (uint32_t i = 0; i < n_parts; ++i) {
         const density_hip_join_part_t& q = parts[i];
@@ -619,20 +588,38 @@ int run_join_container(DeviceCtx* c, const density_hip_join_part_t* parts, uint3
                               paged_pages_base(h.n_chunks, h.total_len, h.chunk_size), ppc, d_lens + K, d_dst_off + K, d_out, d_err, s);
         K += q.chunk_count;
     }
-    prof.mark("join_gather");
+    prof.mark(w.gather_mark);
     if (sealed) {
-        if (e == hipSuccess) e = launch_join_trailers(trailers, live, d_out, cap, (uint32_t)g.n_chunks, d_err, s);
+        if (e == hipSuccess) e = launch_place_trailer(trailers, live, d_out, cap, (uint32_t)g.n_chunks, d_err, s);
         prof.mark("move_trailer");
     }
-    if (e != hipSuccess) { set_error("kernel launch (join)", e); return DENSITY_HIP_ERR_RUNTIME; }
+    const auto named = [&w](const char* front, const char* back) { return std::string(front) + w.name + back; };   // (a refusal's message: nothing is built where none is raised)
+    if (e != hipSuccess) { set_error(named("kernel launch (", ")").c_str(), e); return DENSITY_HIP_ERR_RUNTIME; }
     if (header_out) {
         uint32_t h_err = 0;
         e = read_back(s, d_err, &h_err, header_out, d_out, sizeof(*header_out));
-        if (e != hipSuccess) { set_error("join (device)", e); return DENSITY_HIP_ERR_RUNTIME; }
-        if (h_err & 4u) { set_error("join: a window the call cannot follow (size table, slots or page directory of its chunks)"); return DENSITY_HIP_ERR_FORMAT; }
+        if (e != hipSuccess) { set_error(named("", " (device)").c_str(), e); return DENSITY_HIP_ERR_RUNTIME; }
+        if (h_err & 4u) { set_error(named("", ": a window the call cannot follow (size table, slots or page directory of its chunks)").c_str()); return DENSITY_HIP_ERR_FORMAT; }
         if (h_err) { set_error("container does not fit the output capacity"); return DENSITY_HIP_ERR_CAPACITY; }
     }
     return DENSITY_HIP_OK;
+}
+
+// a slice is a join of one part; its tables lie in plan_decode's arrays of the SOURCE (density_hip_decode_workspace_size), its packed window moves as one run
+int run_slice_container(DeviceCtx* c, const uint8_t* d_in, const density_hip_header_t& h, uint32_t first, uint32_t count, uint8_t* d_out, size_t cap, uint8_t* ws,
+                        hipStream_t s, density_hip_header_t* header_out) {
+    const DecodePlan p = plan_decode(h.algo, h.n_chunks);
+    const density_hip_join_part_t part{d_in, (size_t)h.container_len, &h, first, count};
+    const JoinGeometry g{h.algo, h.chunk_size, (uint32_t)h.flags & (DENSITY_HIP_FLAG_BLOCK_INDEX | DENSITY_HIP_FLAG_CHECKSUM), 1, count, slice_len(h, first, count)};
+    const WindowCall w{p.err(ws), p.produced(ws), p.offsets(ws), p.sizes(ws), p.offsets(ws) + h.n_chunks, (h.flags & DENSITY_HIP_FLAG_SLOTTED) ? slot_stride(h.algo, h.chunk_size) : safe_size(h.algo, h.chunk_size), "slice_layout", "slice_gather", "slice"};
+    return run_windows(c, &part, 1, g, d_out, cap, w, s, header_out);
+}
+
+int run_join_container(DeviceCtx* c, const density_hip_join_part_t* parts, uint32_t n_parts, const JoinGeometry& g, uint8_t* d_out, size_t cap, uint8_t* ws,
+                       hipStream_t s, density_hip_header_t* header_out) {
+    const JoinPlan p = plan_join(g.n_chunks);
+    const WindowCall w{p.err(ws), p.lens(ws), p.src(ws), p.dst_off(ws), nullptr, safe_size(g.algo, g.chunk_size), "join_layout", "join_gather", "join"};
+    return run_windows(c, parts, n_parts, g, d_out, cap, w, s, header_out);
 }
 
 // The seal of the container just written for d_in, in place: every chunk of the INPUT summed (checksum.hip), the trailer behind the container, the flag

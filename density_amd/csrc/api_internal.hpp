@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/density_hip.h"
+#include "common.hpp"
 #include "kernels.hpp"
 
 namespace density {
@@ -42,13 +43,6 @@ inline bool variant(int bits) { return (g_variant & bits) != 0; }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// codec/codec.rs:18-21 with the geometry of chameleon.rs:138-146, cheetah.rs:188-196, lion.rs:317-325
-inline size_t block_bytes(int algo) { return algo == DENSITY_HIP_CHAMELEON ? 256 : algo == DENSITY_HIP_CHEETAH ? 128 : 64; }
-inline size_t sig_bytes(int algo) { return algo == DENSITY_HIP_LION ? 6 : 8; }
-inline size_t safe_size(int algo, size_t n) {
-    const size_t b = block_bytes(algo), s = sig_bytes(algo);
-    return n + (n / b) * s + ((n % b) ? s : 0);
-}
 inline bool valid_algo(int algo) { return algo >= DENSITY_HIP_CHAMELEON && algo <= DENSITY_HIP_LION; }
 // chunk_size 0 = automatic: one chunk is one work-group on one CU, so an input should be cut into at least as many chunks as the device has
 // CUs (256) where that is possible without dropping below 64 KiB (small chunks restart the dictionary and cost ratio), and no finer than that

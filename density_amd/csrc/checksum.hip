@@ -132,27 +132,10 @@ __global__ __launch_bounds__(kSmallThreads) void seal_finish_kernel(uint8_t* __r
     }
 }
 
-// A trailer (n words at `src`) to its place behind the packed container the layout and gather kernels have just written into `dst`: nothing where
-// they raised *err, bit 2 where the capacity does not hold it.
-__global__ __launch_bounds__(kSmallThreads) void move_trailer_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, uint64_t capacity, uint32_t n,
-                                                                     uint32_t* __restrict__ err) {
-    if (*err) return;
-    const uint64_t len = ld64u(dst + 24), at = align16(len), bytes = align16(4ull * n);
-    const uint32_t flags = ld16u(dst + 6);
-    if (at + bytes > capacity) { if (threadIdx.x == 0) atomicOr(err, 2u); return; }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < n; i += kSmallThreads) st32u(dst + at + 4ull * i, ld32u(src + 4ull * i));
-    if (threadIdx.x < at - len) dst[len + threadIdx.x] = 0;
-    if (threadIdx.x < bytes - 4ull * n) dst[at + 4ull * n + threadIdx.x] = 0;
-    if (threadIdx.x == 0) {
-        st16u(dst + 6, flags | DENSITY_HIP_FLAG_CHECKSUM);
-        st64u(dst + 24, at + bytes);
-    }
-}
-
-// The trailer of a joined container: n_parts runs of trailer words, run p to entries [entry, entry + count) of the n-word trailer behind the packed container
-// the join's layout and gather have just written into `dst`; the gap in front and the padding once, as move_trailer_kernel writes them.
-__global__ __launch_bounds__(kSmallThreads) void join_trailers_kernel(TrailerRuns runs, uint32_t n_parts, uint8_t* __restrict__ dst, uint64_t capacity, uint32_t n,
+// The trailer of a packed container: n_parts runs of trailer words, run p to entries [entry, entry + count) of the n-word trailer behind the container the
+// layout and gather kernels have just written into `dst`; the gap in front and the padding once.  Nothing where they raised *err, bit 2 where the capacity
+// does not hold it.
+__global__ __launch_bounds__(kSmallThreads) void place_trailer_kernel(TrailerRuns runs, uint32_t n_parts, uint8_t* __restrict__ dst, uint64_t capacity, uint32_t n,
                                                                       uint32_t* __restrict__ err) {
     if (*err) return;
     const uint64_t len = ld64u(dst + 24), at = align16(len), bytes = align16(4ull * n);
@@ -218,15 +201,16 @@ hipError_t launch_seal(const uint8_t* d_in, uint64_t input_size, uint8_t* d_cont
     return hipGetLastError();
 }
 
-hipError_t launch_move_trailer(const uint8_t* d_trailer, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err, hipStream_t stream) {
-    hipLaunchKernelGGL(move_trailer_kernel, dim3(1), dim3(kSmallThreads), 0, stream, d_trailer, d_container, capacity, n_chunks, d_err);
+hipError_t launch_place_trailer(const TrailerRuns& runs, uint32_t n_parts, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err,
+                                hipStream_t stream) {
+    hipLaunchKernelGGL(place_trailer_kernel, dim3(1), dim3(kSmallThreads), 0, stream, runs, n_parts, d_container, capacity, n_chunks, d_err);
     return hipGetLastError();
 }
 
-hipError_t launch_join_trailers(const TrailerRuns& runs, uint32_t n_parts, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err,
-                                hipStream_t stream) {
-    hipLaunchKernelGGL(join_trailers_kernel, dim3(1), dim3(kSmallThreads), 0, stream, runs, n_parts, d_container, capacity, n_chunks, d_err);
-    return hipGetLastError();
+hipError_t launch_move_trailer(const uint8_t* d_trailer, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err, hipStream_t stream) {
+    TrailerRuns one{};
+    one.p[0] = TrailerRun{d_trailer, 0, n_chunks};
+    return launch_place_trailer(one, 1, d_container, capacity, n_chunks, d_err, stream);
 }
 
 }  // namespace density

@@ -3,7 +3,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/density_hip.h"
+
 namespace density {
+
+// the longest stream n input bytes can come to: a signature per block, whole or ragged — codec/codec.rs:18-21 with the geometry of chameleon.rs:138-146,
+// cheetah.rs:188-196, lion.rs:317-325.  The one definition, for the host's bounds and for the kernels that judge a size-table entry.
+__host__ __device__ inline uint64_t safe_size(int algo, uint64_t n) {
+    const uint64_t b = algo == DENSITY_HIP_CHAMELEON ? 256 : algo == DENSITY_HIP_CHEETAH ? 128 : 64, s = algo == DENSITY_HIP_LION ? 6 : 8;
+    return n + (n / b) * s + ((n % b) ? s : 0);
+}
 
 // hash: (quad * 0x9D6EF916) >> 16 — chameleon.rs:14-15,89; cheetah.rs:14-15; lion.rs:14-15
 constexpr uint32_t kHashMul = 0x9D6EF916u;

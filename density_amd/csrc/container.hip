@@ -204,7 +204,6 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
     for (uint32_t d = 32; d; d >>= 1) v += bperm(lane ^ d, v);
     return v;
 }
-__device__ __forceinline__ uint64_t chameleon_safe_size(uint64_t n) { return n + (n / 256) * 8 + ((n % 256) ? 8 : 0); }   // (api_internal.hpp: safe_size)
 
 // A wave per chunk: may the gather follow this chunk's directory?  1 .. pages_per_chunk pages, every page inside the container, at most a page of bytes in
 // each, the bytes adding up to the size table's entry, and that no more than the chunk's worst case (the packed output is sized by it).  sizes[c]: the
@@ -229,7 +228,7 @@ __global__ __launch_bounds__(256) void check_directory_kernel(const uint8_t* __r
     sum = wave_sum(sum);
     bad = ballot64(bad) != 0;
     const uint64_t first = (uint64_t)c * chunk_bytes, len = total_len - first < chunk_bytes ? total_len - first : chunk_bytes;
-    if (sum != size || size > chameleon_safe_size(len)) bad = true;
+    if (sum != size || size > safe_size(DENSITY_HIP_CHAMELEON, len)) bad = true;
     if (lane == 0) {
         sizes[c] = bad ? 0ull : size;
         if (bad) atomicOr(err, 4u);
@@ -279,133 +278,28 @@ __global__ __launch_bounds__(kCopyThreads) void unpage_kernel(const uint8_t* __r
     if (before + (uint64_t)bytes == size && chunk + 1u < n && t2 < ((0u - (uint32_t)end) & 15u)) out[end + t2] = 0;
 }
 
-// ---- chunks [first, first + count) of a container of any form -> a packed container of their own (density_hip_slice_device) ----
-__device__ __forceinline__ uint64_t safe_size_of(uint32_t algo, uint64_t n) {                    // (api_internal.hpp: safe_size)
-    const uint64_t b = algo == DENSITY_HIP_CHAMELEON ? 256 : algo == DENSITY_HIP_CHEETAH ? 128 : 64, s = algo == DENSITY_HIP_LION ? 6 : 8;
-    return n + (n / b) * s + ((n % b) ? s : 0);
-}
-
-// The window's layout, one work-group.  Where chunk `first`'s stream lies in a packed source only the size table says: the 16-byte-rounded entries are
-// scanned from chunk 0 on (tiles of kScanThreads, the carry of layout_common), from chunk `first` for the other forms (slotted: src_base + i * slot_stride;
-// paged: the gather follows the directory, which check_directory_kernel has held against the table — lens[k] comes from there, 0 where it refused).
-// Left on the device for the gather, per window chunk k: lens[k], src_off[k] (offset in `in`), dst_off[k] (offset in `out`: packed, from out_base), and
-// *run = the bytes from the first stream's start to the last one's end.  Written to `out` (any byte alignment): the header `hdr` with container_len = the
-// last stream's end, the window's size-table entries, zeros over the gaps in front of the payloads and between them.  Refused, with bit 4 of *err and then
-// no gap written and *run = 0: a window entry above its chunk's worst case or its slot, a window stream that ends behind `limit`.  Entries in front of the
-// window are summed, not judged.
-__global__ __launch_bounds__(kScanThreads) void slice_layout_kernel(const uint8_t* __restrict__ in, uint64_t limit, uint32_t algo, uint64_t chunk_bytes, uint64_t total_len,
-                                                                    uint32_t first, uint32_t count, uint64_t src_base, uint64_t slot_stride, uint32_t paged,
-                                                                    uint8_t* __restrict__ out, uint64_t capacity, density_hip_header_t hdr, uint64_t out_base,
-                                                                    uint64_t* lens, uint64_t* __restrict__ src_off, uint64_t* __restrict__ dst_off,
-                                                                    uint64_t* __restrict__ run, uint32_t* __restrict__ err) {
-    __shared__ uint64_t wave_sums[kScanThreads / 64];
-    __shared__ uint64_t s_first, s_end;
-    __shared__ uint32_t s_bad;
-    if (threadIdx.x == 0) { s_first = 0; s_end = 0; s_bad = *err; }                              // (paged: what the directory check raised)
-    __syncthreads();
-    const uint64_t from = (slot_stride || paged) ? first : 0u, to = (uint64_t)first + count;
-    uint64_t carry = 0;
-    for (uint64_t t0 = from; t0 < to; t0 += kScanThreads) {
-        const uint64_t i = t0 + threadIdx.x;
-        const bool in_window = i >= first && i < to;
-        uint64_t raw = 0, keep = 0;
-        if (i < to) {
-            keep = raw = ld32u(in + kHeaderBytes + 4ull * i);
-            if (in_window) {
-                const uint64_t at = i * chunk_bytes, len = total_len - at < chunk_bytes ? total_len - at : chunk_bytes;
-                if (paged) keep = lens[i - first];
-                else if (raw > safe_size_of(algo, len) || (slot_stride && raw > slot_stride)) { keep = 0; atomicOr(&s_bad, 4u); }
-            }
-        }
-        uint64_t tile_total = 0;
-        const uint64_t excl = carry + block_inclusive_scan(align16(keep), wave_sums, &tile_total) - align16(keep);
-        if (in_window) {
-            const uint64_t k = i - first;
-            const uint64_t so = paged ? 0ull : slot_stride ? src_base + i * slot_stride : src_base + excl;
-            if (!paged && (so > limit || keep > limit - so)) { keep = 0; atomicOr(&s_bad, 4u); }  // the stream runs past the container: the gather must not follow it
-            src_off[k] = so;
-            dst_off[k] = excl;                                                                   // (from the scan's start: made the output's below)
-            if (!paged) lens[k] = keep;
-            st32u(out + kHeaderBytes + 4ull * k, (uint32_t)raw);
-            if (k == 0) s_first = excl;
-            if (i == to - 1) s_end = excl + keep;
-        }
-        carry += tile_total;
-    }
-    __syncthreads();
-    const uint64_t end = out_base + (s_end - s_first);
-    const bool bad = s_bad != 0 || end > capacity;
-    for (uint64_t k = threadIdx.x; k < count; k += kScanThreads) {
-        const uint64_t d = out_base + (dst_off[k] - s_first), e = d + lens[k];
-        dst_off[k] = d;
-        if (!bad && k + 1 < count) for (uint64_t p = e; p < align16(e); ++p) out[p] = 0;         // the gap behind the stream is part of the container: zeros
-    }
-    if (threadIdx.x == 0) {
-        *run = bad ? 0ull : end - out_base;
-        if (bad) atomicOr(err, s_bad ? 4u : 2u);
-        const uint64_t len = bad ? out_base : end;
-        st32u(out, hdr.magic);
-        st32u(out + 4, (uint32_t)hdr.algo | (uint32_t)hdr.version << 8 | (uint32_t)hdr.flags << 16);
-        st32u(out + 8, hdr.chunk_size);
-        st32u(out + 12, hdr.n_chunks);
-        st32u(out + 16, (uint32_t)hdr.total_len);
-        st32u(out + 20, (uint32_t)(hdr.total_len >> 32));
-        st32u(out + 24, (uint32_t)len);
-        st32u(out + 28, (uint32_t)(len >> 32));
-    }
-    // (as in layout_encode_kernel: the gaps in front of the payloads are zeros)
-    const uint64_t table_end = kHeaderBytes + 4ull * count, ibase = (table_end + 15) / 16 * 16;
-    const uint64_t iend = ibase + ((hdr.flags & DENSITY_HIP_FLAG_BLOCK_INDEX) ? (hdr.total_len + 255) / 256 : 0);
-    if (threadIdx.x < ibase - table_end) out[table_end + threadIdx.x] = 0;
-    if (threadIdx.x >= 32 && threadIdx.x - 32 < out_base - iend) out[iend + threadIdx.x - 32] = 0;
-}
-
-// The gather of `runs` byte runs: run r is lens[r] bytes from in + src_off[r] to out + dst_off[r], both at any byte phase.  A packed source's window is ONE
-// run (its streams lie as the output wants them, gaps included: the three words are the layout kernel's src_off[0], *run and dst_off[0], read here, so the
-// host never learns them); a slotted source's is a run per chunk.  A run is cut into tiles of kCopyTile; work-groups take tiles in a grid-stride loop and
-// leave the tiles behind a run's end at once.  Inside a tile: bytes up to the first 16-byte boundary of the DESTINATION's address, 16-byte stores fed from
-// loads at whatever phase that gives the source, bytes behind the last whole one (blank_chunks_kernel's cut).  Nothing where *err is set.
-constexpr uint32_t kSliceMaxGroups = 256u * 32u;
-__global__ __launch_bounds__(kCopyThreads) void slice_gather_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ src_off, const uint64_t* __restrict__ lens,
-                                                                    const uint64_t* __restrict__ dst_off, uint32_t runs, uint64_t tiles_per_run, uint8_t* __restrict__ out,
-                                                                    const uint32_t* __restrict__ err) {
-    if (*err) return;
-    const uint64_t units = (uint64_t)runs * tiles_per_run;
-    for (uint64_t u = blockIdx.x; u < units; u += gridDim.x) {
-        const uint64_t r = u / tiles_per_run, t0 = (u % tiles_per_run) * kCopyTile, len = lens[r];
-        if (t0 >= len) continue;
-        const uint32_t n = len - t0 < kCopyTile ? (uint32_t)(len - t0) : kCopyTile;
-        const uint8_t* s = in + src_off[r] + t0;
-        uint8_t* d = out + dst_off[r] + t0;
-        const uint32_t lead = (0u - (uint32_t)(uintptr_t)d) & 15u, head = lead < n ? lead : n;
-        const uint32_t full = (n - head) / 16u, tail_at = head + 16u * full;                     // (full <= 1024: four stores a lane cover it)
-        u32x4 v[4];
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) { const uint32_t i = j * kCopyThreads + threadIdx.x; if (i < full) v[j] = *reinterpret_cast<const u32x4_u*>(s + head + 16ull * i); }
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) { const uint32_t i = j * kCopyThreads + threadIdx.x; if (i < full) *reinterpret_cast<u32x4*>(d + head + 16ull * i) = v[j]; }
-        if (threadIdx.x < head) d[threadIdx.x] = s[threadIdx.x];
-        if (threadIdx.x < n - tail_at) d[tail_at + threadIdx.x] = s[tail_at + threadIdx.x];
-    }
-}
-
-// ---- chunk windows of several containers -> one packed container (density_hip_join_device) ----
-// The joined layout, one work-group.  The parts are walked in order; per part the scan is slice_layout_kernel's (a packed source's size table from chunk 0 on,
-// with the tile carry, for the window's source offset; the other forms from chunk `first`), and a second carry runs across the parts: K, the output's chunk
-// number of the part's first chunk, and `at`, the offset in `out` where its first stream goes — the 16-byte boundary behind the part in front.  Per output
-// chunk for the gather: lens, src (the stream's address, 0 for a paged part's chunk: unpage_kernel moves those) and dst_off.  One run per CHUNK, of the
-// stream's bytes alone: what stands behind a source's stream is its own gap, another part's business, the trailer's padding or nothing at all, so every gap
-// of the output — behind each stream but the last, the parts' seams included — is written here.  Refusals are slice_layout_kernel's, judged inside the
-// windows only: bit 4 of *err, and then no gap is written and container_len says out_base.
-__global__ __launch_bounds__(kScanThreads) void join_layout_kernel(JoinSources parts, uint32_t n_parts, uint32_t algo, uint64_t chunk_bytes, uint8_t* __restrict__ out,
-                                                                   uint64_t capacity, density_hip_header_t hdr, uint64_t out_base, uint64_t* lens,
-                                                                   uint64_t* __restrict__ src, uint64_t* dst_off, uint32_t* __restrict__ err) {
+// ---- chunk windows [first, first + count) of one or several containers of any form -> one packed container (density_hip_slice_device, density_hip_join_device) ----
+// The windows' layout, one work-group.  The parts are walked in order.  Where chunk `first`'s stream lies in a packed part only its size table says: the
+// 16-byte-rounded entries are scanned from chunk 0 on (tiles of kScanThreads, the carry of layout_common), from chunk `first` for the other forms (slotted:
+// src_base + i * slot_stride; paged: the gather follows the directory, which check_directory_kernel has held against the table — lens comes from there, 0
+// where it refused).  A second carry runs across the parts: K, the output's chunk number of the part's first chunk, and `at`, the offset in `out` where its
+// first stream goes — the 16-byte boundary behind the part in front.  Left on the device for the gather, per output chunk: lens, src (the stream's ADDRESS, 0
+// for a paged part's chunk: unpage_kernel moves those) and dst_off (offset in `out`: packed, from out_base); and, where `run` is not null, *run = the bytes
+// from the first stream's start to the last one's end where there is ONE part, 0 for more (a caller with one packed part may move its window as that one
+// run: the streams lie as the output wants them).  Written to `out` (any byte alignment): the header `hdr` with container_len = the last stream's end, every window's
+// size-table entries, zeros over the gaps in front of the payloads and behind each stream but the last, the parts' seams included — what stands behind a
+// source's stream is its own gap, another part's business, the trailer's padding or nothing at all.  Refused, with bit 4 of *err, and then no gap written,
+// container_len = out_base and *run = 0: a window entry above its chunk's worst case or its slot, a window stream that ends behind its part's `limit`.
+// Entries in front of a window are summed, not judged.
+__global__ __launch_bounds__(kScanThreads) void window_layout_kernel(JoinSources parts, uint32_t n_parts, uint32_t algo, uint64_t chunk_bytes, uint8_t* __restrict__ out,
+                                                                     uint64_t capacity, density_hip_header_t hdr, uint64_t out_base, uint64_t* lens,
+                                                                     uint64_t* __restrict__ src, uint64_t* dst_off, uint64_t* __restrict__ run, uint32_t* __restrict__ err) {
     __shared__ uint64_t wave_sums[kScanThreads / 64];
     __shared__ uint64_t s_first, s_end;
     __shared__ uint32_t s_bad;
     if (threadIdx.x == 0) { s_first = 0; s_end = 0; s_bad = *err; }                              // (paged parts: what the directory checks raised)
     __syncthreads();
-    uint64_t K = 0, at = out_base, end = out_base;
+    uint64_t K = 0, at = out_base, end = out_base, span = 0;
     for (uint32_t p = 0; p < n_parts; ++p) {
         const JoinSource& part = parts.p[p];
         const uint8_t* in = part.in;
@@ -423,7 +317,7 @@ __global__ __launch_bounds__(kScanThreads) void join_layout_kernel(JoinSources p
                 if (in_window) {
                     const uint64_t a = i * chunk_bytes, len = total_len - a < chunk_bytes ? total_len - a : chunk_bytes;
                     if (paged) keep = lens[K + (i - first)];
-                    else if (raw > safe_size_of(algo, len) || (slot_stride && raw > slot_stride)) { keep = 0; atomicOr(&s_bad, 4u); }
+                    else if (raw > safe_size((int)algo, len) || (slot_stride && raw > slot_stride)) { keep = 0; atomicOr(&s_bad, 4u); }
                 }
             }
             uint64_t tile_total = 0;
@@ -442,7 +336,8 @@ __global__ __launch_bounds__(kScanThreads) void join_layout_kernel(JoinSources p
             carry += tile_total;
         }
         __syncthreads();
-        const uint64_t first_at = s_first, span = s_end - first_at;
+        const uint64_t first_at = s_first;
+        span = s_end - first_at;
         for (uint64_t k = threadIdx.x; k < count; k += kScanThreads) dst_off[K + k] = at + (dst_off[K + k] - first_at);
         end = at + span;
         at = align16(end);
@@ -455,6 +350,7 @@ __global__ __launch_bounds__(kScanThreads) void join_layout_kernel(JoinSources p
         if (!bad && k + 1 < K) for (uint64_t q = e; q < align16(e); ++q) out[q] = 0;             // the gap behind the stream is part of the container: zeros
     }
     if (threadIdx.x == 0) {
+        if (run) *run = bad || n_parts != 1 ? 0ull : span;
         if (bad) atomicOr(err, s_bad ? 4u : 2u);
         const uint64_t len = bad ? out_base : end;
         st32u(out, hdr.magic);
@@ -473,12 +369,15 @@ __global__ __launch_bounds__(kScanThreads) void join_layout_kernel(JoinSources p
     if (threadIdx.x >= 32 && threadIdx.x - 32 < out_base - iend) out[iend + threadIdx.x - 32] = 0;
 }
 
-// The join's gather: slice_gather_kernel's tiles and cut — bytes up to the DESTINATION's first 16-byte boundary, aligned 16-byte stores fed from loads at
-// whatever phase that gives the source, the tail bytes — with the run's source an address of its own, because the parts lie in different allocations.  A run
-// is one output chunk's stream (tiles_per_run covers the longest a stream can be; the tiles behind a run's end leave at once), so the work follows the bytes
-// moved and no run carries a gap.  src[r] == 0: a paged part's chunk, not moved here.  Nothing where *err is set.
-__global__ __launch_bounds__(kCopyThreads) void join_gather_kernel(const uint64_t* __restrict__ src, const uint64_t* __restrict__ lens, const uint64_t* __restrict__ dst_off,
-                                                                   uint32_t runs, uint64_t tiles_per_run, uint8_t* __restrict__ out, const uint32_t* __restrict__ err) {
+// The gather of `runs` byte runs: run r is lens[r] bytes from the address src[r] (the parts lie in different allocations) to out + dst_off[r], both at any byte
+// phase.  A join's run is one output chunk's stream, so no run carries a gap; a packed slice's window is ONE run (the three words are the layout kernel's
+// src[0], *run and dst_off[0], read here, so the host never learns them) and takes the gaps between its streams along as they stand.  src[r] == 0: a paged
+// part's chunk, not moved here.  A run is cut into tiles of kCopyTile (tiles_per_run covers the longest a run can be); work-groups take tiles in a grid-stride
+// loop and leave the tiles behind a run's end at once.  Inside a tile: bytes up to the first 16-byte boundary of the DESTINATION's address, 16-byte stores fed
+// from loads at whatever phase that gives the source, bytes behind the last whole one (blank_chunks_kernel's cut).  Nothing where *err is set.
+constexpr uint32_t kGatherMaxGroups = 256u * 32u;
+__global__ __launch_bounds__(kCopyThreads) void run_gather_kernel(const uint64_t* __restrict__ src, const uint64_t* __restrict__ lens, const uint64_t* __restrict__ dst_off,
+                                                                  uint32_t runs, uint64_t tiles_per_run, uint8_t* __restrict__ out, const uint32_t* __restrict__ err) {
     if (*err) return;
     const uint64_t units = (uint64_t)runs * tiles_per_run;
     for (uint64_t u = blockIdx.x; u < units; u += gridDim.x) {
@@ -604,35 +503,19 @@ hipError_t launch_unpage(const uint8_t* d_container, uint32_t n_chunks, uint64_t
     return hipGetLastError();
 }
 
-hipError_t launch_slice_layout(const uint8_t* d_container, uint64_t limit, const density_hip_header_t& src, uint32_t first, uint32_t count, uint64_t src_base,
-                               uint64_t slot_stride, bool paged, uint8_t* d_out, uint64_t capacity, density_hip_header_t hdr, uint64_t out_base, uint64_t* d_lens,
-                               uint64_t* d_src_off, uint64_t* d_dst_off, uint64_t* d_run, uint32_t* d_err, hipStream_t stream) {
-    hipLaunchKernelGGL(slice_layout_kernel, dim3(1), dim3(kScanThreads), 0, stream, d_container, limit, (uint32_t)src.algo, (uint64_t)src.chunk_size, src.total_len, first,
-                       count, src_base, slot_stride, paged ? 1u : 0u, d_out, capacity, hdr, out_base, d_lens, d_src_off, d_dst_off, d_run, d_err);
+hipError_t launch_window_layout(const JoinSources& parts, uint32_t n_parts, uint32_t algo, uint64_t chunk_bytes, uint8_t* d_out, uint64_t capacity,
+                                density_hip_header_t hdr, uint64_t out_base, uint64_t* d_lens, uint64_t* d_src, uint64_t* d_dst_off, uint64_t* d_run, uint32_t* d_err,
+                                hipStream_t stream) {
+    hipLaunchKernelGGL(window_layout_kernel, dim3(1), dim3(kScanThreads), 0, stream, parts, n_parts, algo, chunk_bytes, d_out, capacity, hdr, out_base, d_lens, d_src,
+                       d_dst_off, d_run, d_err);
     return hipGetLastError();
 }
 
-hipError_t launch_slice_gather(const uint8_t* d_container, const uint64_t* d_src_off, const uint64_t* d_lens, const uint64_t* d_dst_off, uint32_t runs,
-                               uint64_t longest_run, uint8_t* d_out, const uint32_t* d_err, hipStream_t stream) {
+hipError_t launch_run_gather(const uint64_t* d_src, const uint64_t* d_lens, const uint64_t* d_dst_off, uint32_t runs, uint64_t longest_run, uint8_t* d_out,
+                             const uint32_t* d_err, hipStream_t stream) {
     const uint64_t tiles = (longest_run + kCopyTile - 1) / kCopyTile, units = tiles * runs;
     if (units == 0) return hipSuccess;
-    hipLaunchKernelGGL(slice_gather_kernel, dim3((uint32_t)(units < kSliceMaxGroups ? units : kSliceMaxGroups)), dim3(kCopyThreads), 0, stream, d_container, d_src_off,
-                       d_lens, d_dst_off, runs, tiles, d_out, d_err);
-    return hipGetLastError();
-}
-
-hipError_t launch_join_layout(const JoinSources& parts, uint32_t n_parts, uint32_t algo, uint64_t chunk_bytes, uint8_t* d_out, uint64_t capacity,
-                              density_hip_header_t hdr, uint64_t out_base, uint64_t* d_lens, uint64_t* d_src, uint64_t* d_dst_off, uint32_t* d_err, hipStream_t stream) {
-    hipLaunchKernelGGL(join_layout_kernel, dim3(1), dim3(kScanThreads), 0, stream, parts, n_parts, algo, chunk_bytes, d_out, capacity, hdr, out_base, d_lens, d_src,
-                       d_dst_off, d_err);
-    return hipGetLastError();
-}
-
-hipError_t launch_join_gather(const uint64_t* d_src, const uint64_t* d_lens, const uint64_t* d_dst_off, uint32_t runs, uint64_t longest_run, uint8_t* d_out,
-                              const uint32_t* d_err, hipStream_t stream) {
-    const uint64_t tiles = (longest_run + kCopyTile - 1) / kCopyTile, units = tiles * runs;
-    if (units == 0) return hipSuccess;
-    hipLaunchKernelGGL(join_gather_kernel, dim3((uint32_t)(units < kSliceMaxGroups ? units : kSliceMaxGroups)), dim3(kCopyThreads), 0, stream, d_src, d_lens, d_dst_off,
+    hipLaunchKernelGGL(run_gather_kernel, dim3((uint32_t)(units < kGatherMaxGroups ? units : kGatherMaxGroups)), dim3(kCopyThreads), 0, stream, d_src, d_lens, d_dst_off,
                        runs, tiles, d_out, d_err);
     return hipGetLastError();
 }

@@ -180,36 +180,29 @@ hipError_t launch_check_directory(const uint8_t* d_container, uint32_t n_chunks,
 // gaps between the streams included; nothing where *d_err is set.
 hipError_t launch_unpage(const uint8_t* d_container, uint32_t n_chunks, uint64_t dir_base, uint64_t pages_base, uint32_t pages_per_chunk,
                          const uint64_t* d_sizes, const uint64_t* d_offsets, uint8_t* d_out, const uint32_t* d_err, hipStream_t stream);
-// Chunks [first, first + count) of a container -> a packed container (density_hip_slice_device).  The layout, one work-group: `src` is the source's header,
-// `limit` where its streams end, src_base its payload base (packed: the size table is scanned from chunk 0 for the window's place; slot_stride != 0: slotted;
-// paged: d_lens[k] holds what launch_check_directory left for window chunk k).  Into d_out: `hdr` with its container_len, the window's size-table entries, the
-// zero gaps.  For the gather, count words each: d_lens, d_src_off, d_dst_off, and *d_run = the bytes from the first stream's start to the last one's end.
-// Bit 4 of *d_err: a window entry above its chunk's worst case or slot, a window stream behind `limit` (entries in front of the window are not judged).
-hipError_t launch_slice_layout(const uint8_t* d_container, uint64_t limit, const density_hip_header_t& src, uint32_t first, uint32_t count, uint64_t src_base,
-                               uint64_t slot_stride, bool paged, uint8_t* d_out, uint64_t capacity, density_hip_header_t hdr, uint64_t out_base, uint64_t* d_lens,
-                               uint64_t* d_src_off, uint64_t* d_dst_off, uint64_t* d_run, uint32_t* d_err, hipStream_t stream);
-// `runs` byte runs, d_lens[r] bytes (at most longest_run) from d_container + d_src_off[r] to d_out + d_dst_off[r], any alignment of either; nothing where *d_err is set
-hipError_t launch_slice_gather(const uint8_t* d_container, const uint64_t* d_src_off, const uint64_t* d_lens, const uint64_t* d_dst_off, uint32_t runs,
-                               uint64_t longest_run, uint8_t* d_out, const uint32_t* d_err, hipStream_t stream);
-// Chunk windows of several containers -> one packed container (density_hip_join_device).  The part table travels as a kernel argument (3 KiB of the 4 KiB
-// there are: it is read when the launch is made, so the caller's table may go at once): per part where the container lies, where its streams end (`limit`),
-// its total_len and payload base (paged: unused), how its streams lie (slot_stride: 0 packed, kJoinPaged paged, else slotted), the window.
+// Chunk windows [first, first + count) of one or several containers -> one packed container (density_hip_slice_device: one part; density_hip_join_device).
+// The part table travels as a kernel argument (3 KiB of the 4 KiB there are: it is read when the launch is made, so the caller's table may go at once): per
+// part where the container lies, where its streams end (`limit`), its total_len and payload base (paged: unused), how its streams lie (slot_stride: 0
+// packed — the size table is scanned from chunk 0 for the window's place —, kJoinPaged paged, else slotted), the window.
 constexpr uint32_t kJoinMaxParts = 64;                        // (DENSITY_HIP_JOIN_MAX_PARTS)
 constexpr uint64_t kJoinPaged = ~0ull;
 struct JoinSource { const uint8_t* in; uint64_t limit, total_len, src_base, slot_stride; uint32_t first, count; };
 struct JoinSources { JoinSource p[kJoinMaxParts]; };
-// The layout, one work-group: per part what launch_slice_layout does for one source (for a paged part d_lens[K_p + k] holds what launch_check_directory left for
-// its window chunk k, K_p = the chunks of the parts in front), and across the parts the running output chunk number and destination offset.  Into d_out:
-// `hdr` (n_chunks = the sum of the windows) with its container_len, every window's size-table entries, the zero gaps in front of the payloads and behind every
-// stream but the output's last — the gaps between the parts too.  For the gather, one word per output chunk each: d_lens, d_src (the stream's ADDRESS: the
-// parts lie in different allocations; 0 for a paged part's chunks, which launch_unpage moves) and d_dst_off (offset in d_out).  Bit 4 of *d_err as in
-// launch_slice_layout, judged in every part's window only; then no gap is written.
-hipError_t launch_join_layout(const JoinSources& parts, uint32_t n_parts, uint32_t algo, uint64_t chunk_bytes, uint8_t* d_out, uint64_t capacity,
-                              density_hip_header_t hdr, uint64_t out_base, uint64_t* d_lens, uint64_t* d_src, uint64_t* d_dst_off, uint32_t* d_err, hipStream_t stream);
+// The layout, one work-group, walks the parts in order (for a paged part d_lens[K_p + k] holds what launch_check_directory left for its window chunk k, K_p =
+// the chunks of the parts in front) and carries the running output chunk number and destination offset across them.  Into d_out: `hdr` (n_chunks = the sum
+// of the windows) with its container_len, every window's size-table entries, the zero gaps in front of the payloads and behind every stream but the output's
+// last — the gaps between the parts too.  For the gather, one word per output chunk each: d_lens, d_src (the stream's ADDRESS: the parts lie in different
+// allocations; 0 for a paged part's chunks, which launch_unpage moves) and d_dst_off (offset in d_out).  d_run (nullable): the bytes from the first stream's
+// start to the last one's end where there is ONE part, else 0 — with one packed part, the window as the single run {d_src[0], *d_run, d_dst_off[0]}, gaps as they stand.
+// Bit 4 of *d_err: a window entry above its chunk's worst case or slot, a window stream behind its part's `limit` (entries in front of a window are not
+// judged); then no gap is written and *d_run = 0.
+hipError_t launch_window_layout(const JoinSources& parts, uint32_t n_parts, uint32_t algo, uint64_t chunk_bytes, uint8_t* d_out, uint64_t capacity,
+                                density_hip_header_t hdr, uint64_t out_base, uint64_t* d_lens, uint64_t* d_src, uint64_t* d_dst_off, uint64_t* d_run, uint32_t* d_err,
+                                hipStream_t stream);
 // `runs` byte runs, d_lens[r] bytes (at most longest_run) from address d_src[r] (0: not this kernel's run) to d_out + d_dst_off[r], any alignment of either;
 // nothing where *d_err is set
-hipError_t launch_join_gather(const uint64_t* d_src, const uint64_t* d_lens, const uint64_t* d_dst_off, uint32_t runs, uint64_t longest_run, uint8_t* d_out,
-                              const uint32_t* d_err, hipStream_t stream);
+hipError_t launch_run_gather(const uint64_t* d_src, const uint64_t* d_lens, const uint64_t* d_dst_off, uint32_t runs, uint64_t longest_run, uint8_t* d_out,
+                             const uint32_t* d_err, hipStream_t stream);
 // LDS same-address ordering self-test (ascending lane order within one ds instruction). *d_fail != 0 on violation.
 hipError_t launch_selftest(uint32_t* d_fail, hipStream_t stream);
 
@@ -230,14 +223,14 @@ hipError_t launch_blank_chunks(uint8_t* d_out, uint64_t size, uint32_t chunk, ui
 // does not hold the trailer — the container is then left as it was.
 hipError_t launch_seal(const uint8_t* d_in, uint64_t input_size, uint8_t* d_container, uint64_t capacity, uint32_t* d_geom, uint32_t* d_acc, uint32_t* d_err,
                        hipStream_t stream);
-// a trailer of n_chunks words to its place behind the packed container the layout kernel has just written (density_hip_pack_device)
-hipError_t launch_move_trailer(const uint8_t* d_trailer, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err, hipStream_t stream);
-// ... of n_chunks words gathered from n_parts runs (density_hip_join_device): run p is `count` words at `src`, placed from entry `entry` on; the runs
-// cover entries 0 .. n_chunks - 1 once
+// A trailer of n_chunks words to its place behind the packed container the layout and gather kernels have just written, gathered from n_parts runs: run p is
+// `count` words at `src`, placed from entry `entry` on; the runs cover entries 0 .. n_chunks - 1 once (a join: a run per part; a slice: one run)
 struct TrailerRun { const uint8_t* src; uint32_t entry, count; };
 struct TrailerRuns { TrailerRun p[kJoinMaxParts]; };
-hipError_t launch_join_trailers(const TrailerRuns& runs, uint32_t n_parts, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err,
+hipError_t launch_place_trailer(const TrailerRuns& runs, uint32_t n_parts, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err,
                                 hipStream_t stream);
+// ... as one run, the n_chunks words at d_trailer (density_hip_pack_device, density_hip_unpage_device)
+hipError_t launch_move_trailer(const uint8_t* d_trailer, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err, hipStream_t stream);
 
 // ---- parity.hip (recovery records: the parity blob "DHP1" of include/density_hip.h, and the rebuild behind a verdict decode) ----
 // The blob of d_data (hdr.total_len bytes, any alignment) into d_blob (any alignment): hdr itself, then hdr.n_groups rows of hdr.row_bytes bytes — with

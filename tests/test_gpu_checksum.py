@@ -194,6 +194,40 @@ def test_seal_paged():
         container.pack_device(optr, h1.container_len, zeros(cap)[1], cap, header=h1)
 
 
+@pytest.mark.parametrize("form", ["packed", "slotted"])
+@pytest.mark.parametrize("name", ["b", "a"])
+def test_pack_of_a_sealed_cpu_built_container_places_trailer_gap_and_padding(name, form):
+    """the CPU-built containers of tests/unpage_cases.py (b: 4 chunks, a trailer of exactly 16 bytes; a: 7 chunks, 4 bytes of padding behind it), sealed, in
+    the packed form and in worst-case slots: pack_device writes the model's sealed packed container, whole, and nothing behind it"""
+    import torch
+    import slice_cpu
+    import unpage_cases as uc
+    _, n, chunk, _ = uc.CASES[name]
+    nc, _, _, base, _ = uc.geometry(n, chunk)
+    want = uc.sealed(uc.packed(name), name)
+    blob = uc.packed(name)
+    if form == "slotted":
+        ss, stride = uc.streams(name), slice_cpu.up(slice_cpu.safe_size(0, chunk), 256)
+        blob = np.zeros(base + (nc - 1) * stride + len(ss[-1]), dtype=np.uint8)
+        blob[:base] = uc.packed(name)[:base]
+        for i, s in enumerate(ss):
+            blob[base + i * stride:base + i * stride + len(s)] = np.frombuffer(s, dtype=np.uint8)
+        h = container.parse_header(blob[:32].tobytes())
+        h.flags |= container.FLAG_SLOTTED
+        h.container_len = blob.size
+        blob[:32] = np.frombuffer(bytes(h), dtype=np.uint8)
+    blob = uc.sealed(blob, name)
+    src, sptr = to_device(blob)
+    cap = container.container_bound("chameleon", n, chunk) + container.seal_overhead(n, chunk)
+    out = torch.full((cap + 256,), 0xA5, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    hdr = container.pack_device(sptr, blob.size, out.data_ptr(), cap)
+    got = host(out)
+    assert bytes(hdr) == want[:32].tobytes() and hdr.flags == container.FLAG_BLOCK_INDEX | container.FLAG_CHECKSUM
+    assert np.array_equal(got[:want.size], want), int(np.flatnonzero(got[:want.size] != want)[0])
+    assert (got[want.size:] == 0xA5).all()
+
+
 @pytest.mark.parametrize("algo", ALGOS)
 def test_seal_capacity_one_byte_short(algo):
     """A capacity one byte below the sealed container_len: refused from the caller's header at once, and by the device otherwise; the container stays unsealed."""

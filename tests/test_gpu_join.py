@@ -148,6 +148,17 @@ def test_cpu_built_windows_of_one_container_in_three_forms(seal):
         _decodes_to(want, np.concatenate([a[3 * chunk:6 * chunk], a[chunk:3 * chunk], a[:chunk], a[6 * chunk:]]))
 
 
+def test_a_packed_window_as_the_only_part_has_zeros_in_its_gaps_whatever_the_source_holds_there():
+    """where a one-part join is not a slice (tests/test_gpu_slice.py: the slice takes the gap's byte along)"""
+    from test_gpu_slice import gap_plants
+    blob = uc.packed("a")
+    want = join_cpu.join_containers([(blob, 1, 2)])
+    assert np.array_equal(want, slice_cpu.slice_container(blob, 1, 2))
+    for bad, _, _, _ in gap_plants(blob, 1, 2):
+        hdr, got, cap = _join([(bad, 1, 2)])
+        _check_output(got, hdr, want, cap)
+
+
 # ---- 2. the library's own containers ----
 
 @functools.lru_cache(maxsize=None)
@@ -193,6 +204,27 @@ def test_a_container_split_in_two_joins_back_to_what_encode_device_writes(algo, 
         _check_output(got, hdr, whole, cap)
     if seal:
         _decodes_to(got[:whole.size], data)
+
+
+@pytest.mark.parametrize("seal", [False, True])
+@pytest.mark.parametrize("algo,form", list(vc.SHAPES))
+def test_a_slice_is_a_join_of_one_part(algo, form, seal):
+    import torch
+    _, _, sealed_blob, plain = _own(algo, form)
+    blob = sealed_blob if seal else plain
+    h = container.parse_header(bytes(blob[:32]))
+    d = _upload(blob)
+    for first, count in slice_cpu.windows(vc.n_chunks(algo, form)):
+        row = (d.data_ptr(), blob.size, h, first, count)
+        cap = container.join_bound([row])
+        assert cap == container.slice_bound(h, first, count)
+        joined, sliced = _output(cap), _output(cap)
+        hj = container.join_device([row], joined.data_ptr(), cap, stream=_stream())
+        hs = container.slice_device(d.data_ptr(), blob.size, first, count, sliced.data_ptr(), cap, header=h, stream=_stream())
+        assert bytes(hj) == bytes(hs) and 32 < hj.container_len <= cap
+        joined, sliced = joined.cpu().numpy(), sliced.cpu().numpy()
+        assert np.array_equal(joined[:hj.container_len], sliced[:hj.container_len]), (first, count)
+        assert (joined[hj.container_len:] == FILL).all() and (sliced[hj.container_len:] == FILL).all()
 
 
 @pytest.mark.parametrize("seal", [False, True])

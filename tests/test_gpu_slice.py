@@ -172,6 +172,37 @@ def test_the_host_pointer_form():
             container.slice(blob, 1, 2, out[:want.size - 1])
 
 
+# ---- the one place where a slice is not a one-part join: a packed window moves as ONE run, the gaps between its streams as they stand ----
+
+def gap_plants(blob, first, count):
+    """[(the blob with one byte of the gap behind chunk k's stream changed to `value`, offset of that byte from chunk `first`'s stream, k is the window's
+    last chunk, value)] for the last two chunks of window [first, first + count) of a packed container (tests/test_gpu_join.py plants the same)"""
+    n = container.parse_header(bytes(blob[:32])).n_chunks
+    sizes = [uc.get32(blob, 32 + 4 * i) for i in range(n)]
+    starts = [_payload_at(blob, 0, n) + sum(slice_cpu.up(v, 16) for v in sizes[:i]) for i in range(n)]
+    out = []
+    for k in (first + count - 2, first + count - 1):
+        assert sizes[k] % 16 != 0, "a gap stands behind the stream"
+        at = starts[k] + sizes[k] + (16 - sizes[k] % 16) // 2
+        assert at < starts[k + 1] and not blob[at]
+        for value in (FILL, FILL ^ 0xFF):
+            bad = blob.copy()
+            bad[at] = value
+            out.append((bad, at - starts[first], k == first + count - 1, value))
+    return out
+
+
+def test_a_packed_window_takes_the_gaps_between_its_streams_as_they_stand():
+    blob = uc.packed("a")
+    intact = slice_cpu.slice_container(blob, 1, 2)
+    for bad, rel, behind_the_last, value in gap_plants(blob, 1, 2):
+        want = intact.copy()
+        if not behind_the_last:
+            want[_payload_at(blob, 1, 2) + rel] = value                             # ... and nowhere else
+        hdr, got, cap = _slice(bad, 1, 2)
+        _check_output(got, hdr, want, cap)                                          # (behind the window's last stream: not the slice's byte, the fill stays)
+
+
 # ---- the scan's carry: more chunks in front of the window than one tile of the scan holds ----
 
 @functools.lru_cache(maxsize=None)
