@@ -19,7 +19,7 @@ extern "C" {
 }
 
 /// include/density_hip.h section 2, sealed containers (DENSITY_HIP_FLAG_CHECKSUM): what a CPU reader and a host-pointer producer link.  The device-pointer calls
-/// (density_hip_checksum_device, density_hip_seal_device, density_hip_decode_device_verdicts, density_hip_parity_device, density_hip_decode_device_recover) take a hipStream_t and belong to a caller that already binds HIP; they are declared here in step with the header.
+/// (density_hip_checksum_device, density_hip_seal_device, density_hip_decode_device_verdicts, density_hip_parity_device, density_hip_parity_update_device, density_hip_decode_device_recover) take a hipStream_t and belong to a caller that already binds HIP; they are declared here in step with the header.
 pub mod sealed {
     pub const DENSITY_HIP_FLAG_CHECKSUM: u16 = 8;
     pub const DENSITY_HIP_ERR_CHECKSUM: i32 = 6;
@@ -60,6 +60,15 @@ pub mod sealed {
         pub fn density_hip_parity2_device(d_input: *const core::ffi::c_void, input_size: usize, chunk_size: usize, n_groups: u32, d_parity: *mut core::ffi::c_void,
                                           parity_capacity: usize, stream: *mut core::ffi::c_void) -> i32;
         pub fn density_hip_parity2(input: *const u8, input_size: usize, chunk_size: usize, n_groups: u32, parity: *mut u8, parity_capacity: usize) -> usize;
+        /// parity update: the blob at d_parity kept current after input bytes [offset, offset + old_size) changed from d_old to d_new (a same-size edit, or one
+        /// of the tail: append, truncation); only the rows of the edited chunks are touched.  parity_header, header_out: host, each optional.
+        pub fn density_hip_parity_update_header(header: *const DensityHipParityHeader, offset: u64, old_size: usize, new_size: usize,
+                                                header_out: *mut DensityHipParityHeader) -> i32;
+        pub fn density_hip_parity_update_device(d_parity: *mut core::ffi::c_void, parity_size: usize, parity_header: *const DensityHipParityHeader, offset: u64,
+                                                d_old: *const core::ffi::c_void, old_size: usize, d_new: *const core::ffi::c_void, new_size: usize,
+                                                stream: *mut core::ffi::c_void, header_out: *mut DensityHipParityHeader) -> i32;
+        pub fn density_hip_parity_update(parity: *mut u8, parity_size: usize, offset: u64, old_data: *const u8, old_size: usize, new_data: *const u8,
+                                         new_size: usize) -> usize;
         pub fn density_hip_decode_device_recover(d_container: *const core::ffi::c_void, container_size: usize, header: *const DensityHipHeader, d_parity: *const core::ffi::c_void,
                                                  parity_size: usize, parity_header: *const DensityHipParityHeader, d_output: *mut core::ffi::c_void, output_capacity: usize,
                                                  d_workspace: *mut core::ffi::c_void, workspace_size: usize, stream: *mut core::ffi::c_void, d_verdicts: *mut u32,

@@ -94,6 +94,9 @@ SYMBOLS.update({
     "density_hip_parity2_size": (_SZ, [_SZ, _SZ, ctypes.c_uint32]),
     "density_hip_parity2_device": (_I, [_VP, _SZ, _SZ, ctypes.c_uint32, _VP, _SZ, _VP]),
     "density_hip_parity2": (_SZ, [_VP, _SZ, _SZ, ctypes.c_uint32, _VP, _SZ]),
+    "density_hip_parity_update_header": (_I, [ctypes.POINTER(ParityHeader), ctypes.c_uint64, _SZ, _SZ, ctypes.POINTER(ParityHeader)]),
+    "density_hip_parity_update_device": (_I, [_VP, _SZ, ctypes.POINTER(ParityHeader), ctypes.c_uint64, _VP, _SZ, _VP, _SZ, _VP, ctypes.POINTER(ParityHeader)]),
+    "density_hip_parity_update": (_SZ, [_VP, _SZ, ctypes.c_uint64, _VP, _SZ, _VP, _SZ]),
     "density_hip_decode_device_recover": (_I, [_VP, _SZ, ctypes.POINTER(Header), _VP, _SZ, ctypes.POINTER(ParityHeader), _VP, _SZ, _VP, _SZ, _VP, _VP, ctypes.c_uint,
                                                ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     "density_hip_decode_recover": (_SZ, [_VP, _SZ, _VP, _SZ, _VP, _SZ, ctypes.POINTER(ctypes.c_uint32), _SZ, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint32),

@@ -541,6 +541,38 @@ def parity2(input, chunk_size, n_groups, output):
     return r
 
 
+def parity_update_header(header, offset, old_size, new_size):
+    """The header a parity blob with `header` (a ParityHeader) has after an edit of its input — bytes [offset, offset + old_size) replaced by new_size bytes: a
+    same-size edit anywhere, or an edit of the tail (append, truncation) — by host arithmetic alone; raises EncodeError for an edit parity_update_device refuses."""
+    after = _lib.ParityHeader()
+    _check(_lib.lib().density_hip_parity_update_header(ctypes.byref(header), offset, old_size, new_size, ctypes.byref(after)), EncodeError)
+    return after
+
+
+def parity_update_device(d_parity, parity_size, offset, d_old, old_size, d_new, new_size, parity_header=None, stream=0, want_header=True):
+    """Enqueue the update of the parity blob (either version) at d_parity after an edit of its input: bytes [offset, offset + old_size) held the old_size bytes at
+    d_old and hold the new_size bytes at d_new now (all three on the device, at any alignment) — a same-size edit anywhere, or one of the tail: append, truncation.
+    The blob becomes what parity_device / parity2_device writes for the edited input; only the rows of the edited chunks are touched.  A wrong `old` cannot be
+    seen: it gives a wrong blob, whose rebuilds fail the trailer check.  With parity_header (a ParityHeader) nothing synchronises; None: read back first.  Returns
+    the blob's new header (host arithmetic) or None."""
+    hdr = _lib.ParityHeader() if want_header else None
+    rc = _lib.lib().density_hip_parity_update_device(d_parity, parity_size, ctypes.byref(parity_header) if parity_header is not None else None, offset, d_old, old_size,
+                                                     d_new, new_size, stream, ctypes.byref(hdr) if want_header else None)
+    _check(rc, EncodeError)
+    return hdr
+
+
+def parity_update(parity, offset, old, new):
+    """parity_update_device on host arrays, staged whole: the writable blob `parity` is updated in place; returns the blob's size."""
+    pa, pn, k1 = _rw(parity)
+    oa, on, k2 = _ro(old)
+    na, nn, k3 = _ro(new)
+    r = _lib.lib().density_hip_parity_update(pa, pn, offset, oa, on, na, nn)
+    if r == 0:
+        raise EncodeError(_lib.last_error())
+    return r
+
+
 def decode_device_recover(d_container, container_size, d_parity, parity_size, d_out, cap, d_verdicts, header=None, parity_header=None, stream=0, workspace=(0, 0),
                           blank=True, sync=True):
     """decode_device_verdicts, then every chunk that is the only damaged one of its parity group — with a version-2 blob (parity2_device): one of the only two —

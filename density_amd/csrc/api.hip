@@ -381,6 +381,19 @@ int check_parity_header(const density_hip_parity_header_t& ph, const density_hip
     return DENSITY_HIP_OK;
 }
 
+bool parity_header_is_blobs(const density_hip_parity_header_t& ph) {
+    if (ph.magic != DENSITY_HIP_PARITY_MAGIC || (ph.version != 1 && ph.version != 2) || !valid_chunk(ph.chunk_size)) return false;
+    const density_hip_parity_header_t want = make_parity_header(ph.total_len, ph.chunk_size, ph.n_groups, ph.version);
+    if (chunk_count(ph.total_len, ph.chunk_size) != ph.n_chunks || (ph.n_chunks && !ph.n_groups) || ph.n_groups != want.n_groups || ph.row_bytes != want.row_bytes) return false;
+    return ph.version != 2 || parity_group_members(ph) <= kParityQMembers;
+}
+
+int check_parity_update(const density_hip_parity_header_t& ph, size_t parity_size, uint64_t offset, size_t old_size, size_t new_size, density_hip_parity_header_t* after) {
+    if (!parity_header_is_blobs(ph)) { set_error("bad parity header"); return DENSITY_HIP_ERR_FORMAT; }
+    if (parity_size < parity_bytes(ph)) { set_error("parity blob shorter than its header and rows"); return DENSITY_HIP_ERR_FORMAT; }
+    return density_hip_parity_update_header(&ph, offset, old_size, new_size, after);
+}
+
 size_t parity_size_of(uint8_t version, size_t input_size, size_t chunk_size, uint32_t n_groups) {
     if (!valid_chunk(chunk_size) || chunk_count(input_size, chunk_size) > 0xffffffffull || (input_size && !n_groups)) return 0;
     const density_hip_parity_header_t ph = make_parity_header(input_size, chunk_size, n_groups, version);
@@ -925,6 +938,57 @@ int density_hip_parity_device(const void* d_input, size_t input_size, size_t chu
 }
 int density_hip_parity2_device(const void* d_input, size_t input_size, size_t chunk_size, uint32_t n_groups, void* d_parity, size_t parity_capacity, void* stream) {
     return parity_device(2, d_input, input_size, chunk_size, n_groups, d_parity, parity_capacity, stream);
+}
+
+// the one place the geometry rules of a parity update live (include/density_hip.h): density_hip_parity_update_device and density_hip_parity_update go through it
+int density_hip_parity_update_header(const density_hip_parity_header_t* header, uint64_t offset, size_t old_size, size_t new_size, density_hip_parity_header_t* header_out) {
+    g_last_error.clear();
+    if (!header || !parity_header_is_blobs(*header)) { set_error("parity update: not a parity blob's header"); return DENSITY_HIP_ERR_ARGUMENT; }
+    const density_hip_parity_header_t& ph = *header;
+    const bool same_size = old_size == new_size && offset <= ph.total_len && old_size <= ph.total_len - offset;
+    const bool tail = offset <= ph.total_len && old_size == ph.total_len - offset;
+    if (!same_size && !tail) { set_error("parity update: neither a same-size edit inside the input nor an edit of its tail"); return DENSITY_HIP_ERR_ARGUMENT; }
+    const uint64_t total = same_size ? ph.total_len : offset + new_size;
+    if (total < offset || chunk_count(total, ph.chunk_size) > 0xffffffffull) { set_error("parity update: the edited input is too long"); return DENSITY_HIP_ERR_ARGUMENT; }
+    density_hip_parity_header_t after = make_parity_header(total, ph.chunk_size, ph.n_groups, ph.version);
+    if (after.n_groups != ph.n_groups || (after.n_chunks && !after.n_groups) || after.row_bytes != ph.row_bytes) {
+        set_error("parity update: the edited input's blob has other rows than this one (fewer chunks than groups, or a single short chunk changing length): make a new blob");
+        return DENSITY_HIP_ERR_ARGUMENT;
+    }
+    if (after.version == 2 && parity_group_members(after) > kParityQMembers) { set_error("parity update: a group of more than 255 chunks (version 2): make a new blob"); return DENSITY_HIP_ERR_ARGUMENT; }
+    if (header_out) *header_out = after;
+    return DENSITY_HIP_OK;
+}
+
+int density_hip_parity_update_device(void* d_parity, size_t parity_size, const density_hip_parity_header_t* parity_header, uint64_t offset, const void* d_old, size_t old_size,
+                                     const void* d_new, size_t new_size, void* stream, density_hip_parity_header_t* header_out) {
+    g_last_error.clear();
+    if (!d_parity || (!d_old && old_size) || (!d_new && new_size)) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
+    if (parity_size < sizeof(density_hip_parity_header_t)) { set_error("parity blob shorter than its header"); return DENSITY_HIP_ERR_FORMAT; }
+    density_hip_parity_header_t after;
+    if (parity_header) {                                                      // (everything is decided before a device is acquired)
+        if (const int rc = check_parity_update(*parity_header, parity_size, offset, old_size, new_size, &after)) return rc;
+        if (header_out) *header_out = after;
+        if (!old_size && !new_size) return DENSITY_HIP_OK;
+    }
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return DENSITY_HIP_ERR_RUNTIME;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (!parity_header) {
+        density_hip_parity_header_t ph;
+        hipError_t e = hipMemcpyAsync(&ph, d_parity, sizeof(ph), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { set_error("parity header read-back", e); return DENSITY_HIP_ERR_RUNTIME; }
+        if (const int rc = check_parity_update(ph, parity_size, offset, old_size, new_size, &after)) return rc;
+        if (header_out) *header_out = after;
+        if (!old_size && !new_size) return DENSITY_HIP_OK;
+    }
+    Profiler prof(c, s);
+    const hipError_t e = launch_parity_update((uint8_t*)d_parity, after, offset, (const uint8_t*)d_old, old_size, (const uint8_t*)d_new, new_size, s);
+    prof.mark("parity_update");
+    if (e != hipSuccess) { set_error("kernel launch (parity update)", e); return DENSITY_HIP_ERR_RUNTIME; }
+    return DENSITY_HIP_OK;
 }
 
 int density_hip_checksum_device(const void* d_data, size_t size, size_t chunk_size, uint32_t* d_sums, void* stream) {

@@ -418,4 +418,29 @@ size_t density_hip_parity2(const uint8_t* input, size_t input_size, size_t chunk
     return parity_staged(2, input, input_size, chunk_size, n_groups, parity, parity_capacity);
 }
 
+// staged whole: the old bytes and the new ones side by side in the input's staging buffer, the blob in the output's, updated there and brought back
+size_t density_hip_parity_update(uint8_t* parity, size_t parity_size, uint64_t offset, const uint8_t* old_data, size_t old_size, const uint8_t* new_data, size_t new_size) {
+    g_last_error.clear();
+    if (!parity || (!old_data && old_size) || (!new_data && new_size)) { set_error("bad argument"); return 0; }
+    density_hip_parity_header_t ph, after;
+    if (parity_size < sizeof(ph)) { set_error("parity blob shorter than its header"); return 0; }
+    std::memcpy(&ph, parity, sizeof(ph));
+    if (check_parity_update(ph, parity_size, offset, old_size, new_size, &after) != DENSITY_HIP_OK) return 0;
+    const size_t bytes = parity_bytes(ph), new_at = align_up(old_size, kAlign);
+    if (!old_size && !new_size) return bytes;
+    DeviceCtx* c = acquire_ctx();
+    if (!c) return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipError_t e = ensure_staging(c, new_at + new_size, bytes, 0);
+    if (e == hipSuccess) e = copy_host_side_pinned(c->stage_in.p, old_data, old_size, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = copy_host_side_pinned((uint8_t*)c->stage_in.p + new_at, new_data, new_size, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = copy_host_side_pinned(c->stage_out.p, parity, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) { set_error("staging (H2D)", e); return 0; }
+    e = launch_parity_update((uint8_t*)c->stage_out.p, after, offset, (const uint8_t*)c->stage_in.p, old_size, (const uint8_t*)c->stage_in.p + new_at, new_size, c->stream);
+    if (e != hipSuccess) { set_error("kernel launch (parity update)", e); return 0; }
+    e = copy_host_side_pinned(parity, c->stage_out.p, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) { set_error("staging (D2H)", e); return 0; }
+    return bytes;
+}
+
 }  // extern "C"

@@ -377,6 +377,12 @@ int run_decode_verdicts(DeviceCtx* c, const uint8_t* d_in, size_t container_size
                         hipStream_t s, size_t ws_size, uint32_t* d_verdicts, unsigned flags, uint32_t* damaged_out, const Recovery* rec = nullptr);
 // a parity blob's header against the container it is to serve and the bytes there are of it: DENSITY_HIP_OK / _ERR_FORMAT / _ERR_ARGUMENT (include/density_hip.h)
 int check_parity_header(const density_hip_parity_header_t& ph, const density_hip_header_t& h, size_t parity_size);
+// a parity header that stands for itself — no container to hold it against —: magic, version, a valid chunk size, n_chunks, n_groups and row_bytes as the formulas
+// give them for its total_len, version 2 with groups of at most 255
+bool parity_header_is_blobs(const density_hip_parity_header_t& ph);
+// a parity update (density_hip_parity_update_device): the blob's header and the bytes there are of it (DENSITY_HIP_ERR_FORMAT), then the edit through
+// density_hip_parity_update_header (DENSITY_HIP_ERR_ARGUMENT); *after: the header behind the edit
+int check_parity_update(const density_hip_parity_header_t& ph, size_t parity_size, uint64_t offset, size_t old_size, size_t new_size, density_hip_parity_header_t* after);
 // density_hip_parity_size (version 1) and density_hip_parity2_size (version 2)
 size_t parity_size_of(uint8_t version, size_t input_size, size_t chunk_size, uint32_t n_groups);
 // the seal of the container just encoded for d_in (`ws`: plan_seal(n).total bytes); `header`: the caller's copy of its header, or nullptr

@@ -236,6 +236,12 @@ hipError_t launch_move_trailer(const uint8_t* d_trailer, uint8_t* d_container, u
 // The blob of d_data (hdr.total_len bytes, any alignment) into d_blob (any alignment): hdr itself, then hdr.n_groups rows of hdr.row_bytes bytes — with
 // hdr.version 2 as many Q rows (GF(2^8), from the same loads) behind them.
 hipError_t launch_parity_rows(const uint8_t* d_data, const density_hip_parity_header_t& hdr, uint8_t* d_blob, hipStream_t stream);
+// The blob at d_blob (any alignment) brought up to date after an edit of its input: input bytes [offset, offset + old_size) held d_old and hold d_new (new_size
+// bytes; the shorter of the two counts as zero-padded; both at any alignment) now.  `after`: the blob's header after the edit (density_hip_parity_update_header) —
+// version, chunk_size, n_groups and row_bytes are the blob's own, n_chunks and total_len are written into the blob.  Only the rows of the groups the edited chunks
+// belong to are read and written, every 16-byte slot by one lane; an edit inside one chunk takes only the row tiles it covers.  A zero-length edit launches nothing.
+hipError_t launch_parity_update(uint8_t* d_blob, const density_hip_parity_header_t& after, uint64_t offset, const uint8_t* d_old, uint64_t old_size, const uint8_t* d_new,
+                                uint64_t new_size, hipStream_t stream);
 // Behind launch_chunk_verdicts.  d_victim[g] (n_groups words of scratch) = the only chunk of group g with verdict DENSITY_HIP_CHUNK_DAMAGED, if there is exactly
 // one: its bytes in d_out become row g of d_rows (n_groups rows of row_bytes bytes, any alignment) XOR the other members' bytes, and d_acc[victim] = 0.
 // with_q (a version-2 blob: n_groups Q rows behind those; groups of at most 255): d_victim[g] names the group's only TWO damaged chunks as well, and both are

@@ -16,6 +16,9 @@
 // below; the <false> instances are the version-1 kernels.  One pass makes both rows: the members are walked from the last down and Q follows Horner's rule,
 // Q = 2·Q ^ D, on four packed bytes a word (xtime), so no member needs a constant of its own.  With both rows a group's plan word may name TWO damaged members
 // at places a < b, with the two constants of the solve  D_a = c1·Pxy ^ c2·Qxy,  D_b = Pxy ^ D_a  (Pxy, Qxy: the rows XOR the sums over the intact members).
+//
+// The blob is a linear code over the zero-padded input, so a blob is kept current after an edit of its input by the same code applied to old ^ new
+// (parity_update_kernel): only the rows of the edited chunks are read and written, in the same tiles and slots, each slot by the one lane that owns it.
 #include "checksum_dev.hpp"
 #include "kernels.hpp"
 
@@ -354,6 +357,84 @@ __global__ __launch_bounds__(256) void recover_verify_kernel(const uint32_t* __r
     }
 }
 
+// The 16 bytes at input position `pos` of an edit's side: `p` holds the input's bytes [base, base + size) and every other position counts as zero — clipped on BOTH
+// sides, where load16_clipped clips at the end only.
+__device__ __forceinline__ u32x4 load16_window(const uint8_t* p, uint64_t base, uint64_t size, uint64_t pos) {
+    if (pos >= base + size || pos + 16u <= base) return u32x4{0u, 0u, 0u, 0u};
+    if (pos >= base && base + size - pos >= 16u) return load16(p + (pos - base));
+    uint32_t w[4];
+#pragma unroll
+    for (uint32_t q = 0; q < 4u; ++q) {
+        w[q] = 0u;
+#pragma unroll
+        for (uint32_t b = 0; b < 4u; ++b) {
+            const uint64_t i = pos + 4u * q + b - base;                      // (in front of the window: wraps to a value no size reaches)
+            if (i < size) w[q] |= (uint32_t)p[i] << (8u * b);
+        }
+    }
+    const u32x4 v{w[0], w[1], w[2], w[3]};
+    return v;
+}
+
+// An edit of the blob's input, as launch_parity_update hands it over: input bytes [offset, offset + old_size) held `old_data` and hold `new_data` (new_size bytes,
+// the shorter of the two zero-padded) now — chunks [m0, m1) are touched, of tg = min(m1 - m0, n_groups) groups, and of every row the tiles [tile0, tile0 + tiles).
+struct ParityEdit {
+    const uint8_t *old_data, *new_data;
+    uint64_t offset, old_size, new_size, total_len;                          // total_len, n_chunks: of the input after the edit
+    uint32_t chunk, n_groups, row_bytes, n_chunks, m0, m1, tg, tile0, tiles;
+};
+
+// The blob brought up to date after an edit of its input.  The blob is linear over the zero-padded input, so the edit's effect on it is the same code applied to
+// delta = old ^ new: P row g ^= delta of every touched member, Q row g ^= 2^place · delta.  A unit is a tile of a touched group's row; every 16-byte slot of it
+// belongs to one lane, which reads, modifies and writes it — no atomics, and rows of groups no touched chunk belongs to are not written.  The touched members of a
+// group stand at consecutive places, so Q follows Horner from the last one down, q = 2·q ^ delta, and one product with 2^(place of the first) a slot ends it.
+// Work-group 0 writes the header words the edit changes (nobody reads the header here).
+template <bool kQ>
+__global__ __launch_bounds__(kParThreads) void parity_update_kernel(uint8_t* blob, ParityEdit e) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        st32u(blob + 12, e.n_chunks);
+        st32u(blob + 16, (uint32_t)e.total_len);
+        st32u(blob + 20, (uint32_t)(e.total_len >> 32));
+    }
+    const uint64_t units = (uint64_t)e.tg * e.tiles;
+    for (uint64_t u = blockIdx.x; u < units; u += gridDim.x) {
+        const uint32_t first = e.m0 + (uint32_t)(u / e.tiles), t0 = (e.tile0 + (uint32_t)(u % e.tiles)) * kParTile;   // (first: the group's first touched member)
+        const uint32_t g = first % e.n_groups, members = (uint32_t)(((uint64_t)e.m1 - first + e.n_groups - 1u) / e.n_groups);
+        u32x4 p[kParLoads], q[kParLoads];
+        uint32_t off[kParLoads];
+#pragma unroll
+        for (uint32_t j = 0; j < kParLoads; ++j) {
+            p[j] = q[j] = u32x4{0u, 0u, 0u, 0u};
+            off[j] = t0 + (j * kParThreads + threadIdx.x) * 16u;
+        }
+#pragma unroll 2
+        for (uint32_t i = members; i-- > 0u;) {
+            const uint64_t at = ((uint64_t)first + (uint64_t)i * e.n_groups) * e.chunk;   // (a slot that begins inside the row ends inside the member's chunk: row_bytes <= chunk)
+            u32x4 d[kParLoads];
+#pragma unroll
+            for (uint32_t j = 0; j < kParLoads; ++j)
+                d[j] = off[j] < e.row_bytes ? load16_window(e.old_data, e.offset, e.old_size, at + off[j]) ^ load16_window(e.new_data, e.offset, e.new_size, at + off[j])
+                                            : u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+            for (uint32_t j = 0; j < kParLoads; ++j) {
+                p[j] ^= d[j];
+                if (kQ) q[j] = xtime(q[j]) ^ d[j];
+            }
+        }
+        const uint32_t c = kQ ? gf_pow2(first / e.n_groups) : 1u;
+        uint8_t* row = blob + kHeaderBytes + (uint64_t)g * e.row_bytes;
+#pragma unroll
+        for (uint32_t j = 0; j < kParLoads; ++j) {
+            if (off[j] >= e.row_bytes) continue;
+            store16(row + off[j], load16(row + off[j]) ^ p[j]);
+            if (kQ) {
+                uint8_t* qrow = row + (uint64_t)e.n_groups * e.row_bytes;
+                store16(qrow + off[j], load16(qrow + off[j]) ^ gf_times(c, q[j]));
+            }
+        }
+    }
+}
+
 uint32_t grid_for(uint64_t units) { return (uint32_t)(units < 1 ? 1 : units < kParMaxGroups ? units : kParMaxGroups); }
 
 template <bool kQ>
@@ -385,6 +466,24 @@ hipError_t launch_parity_rows(const uint8_t* d_data, const density_hip_parity_he
     const uint64_t units = (uint64_t)hdr.n_groups * ((hdr.row_bytes + kParTile - 1) / kParTile);
     if (hdr.version == 2) hipLaunchKernelGGL(parity_rows_kernel<true>, dim3(grid_for(units)), dim3(kParThreads), 0, stream, d_data, hdr, d_blob);
     else hipLaunchKernelGGL(parity_rows_kernel<false>, dim3(grid_for(units)), dim3(kParThreads), 0, stream, d_data, hdr, d_blob);
+    return hipGetLastError();
+}
+
+hipError_t launch_parity_update(uint8_t* d_blob, const density_hip_parity_header_t& after, uint64_t offset, const uint8_t* d_old, uint64_t old_size, const uint8_t* d_new,
+                                uint64_t new_size, hipStream_t stream) {
+    const uint64_t span = old_size > new_size ? old_size : new_size, chunk = after.chunk_size;
+    if (span == 0 || after.n_groups == 0) return hipSuccess;
+    const uint64_t m0 = offset / chunk, m1 = (offset + span + chunk - 1) / chunk;
+    ParityEdit e{d_old, d_new, offset, old_size, new_size, after.total_len, after.chunk_size, after.n_groups, after.row_bytes, after.n_chunks, (uint32_t)m0, (uint32_t)m1,
+                 (uint32_t)std::min<uint64_t>(m1 - m0, after.n_groups), 0u, (after.row_bytes + kParTile - 1) / kParTile};
+    if (m1 - m0 == 1) {                                                      // one chunk: only the tiles of its row the edit covers — a 100-byte edit is one work-group
+        const uint64_t lo = offset - m0 * chunk, hi = std::min<uint64_t>(lo + span, after.row_bytes);
+        e.tile0 = (uint32_t)(lo / kParTile);
+        e.tiles = hi > lo ? (uint32_t)((hi + kParTile - 1) / kParTile) - e.tile0 : 0u;
+    }
+    const uint32_t grid = grid_for((uint64_t)e.tg * e.tiles);
+    if (after.version == 2) hipLaunchKernelGGL(parity_update_kernel<true>, dim3(grid), dim3(kParThreads), 0, stream, d_blob, e);
+    else hipLaunchKernelGGL(parity_update_kernel<false>, dim3(grid), dim3(kParThreads), 0, stream, d_blob, e);
     return hipGetLastError();
 }
 

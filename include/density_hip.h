@@ -306,7 +306,8 @@ size_t density_hip_slice(const uint8_t* container, size_t container_size, uint32
  *     reports DENSITY_HIP_ERR_FORMAT / _CAPACITY.
  *   density_hip_join: the host-pointer form, staged whole; returns the bytes written, 0 on failure with density_hip_last_error() set.
  * Profiling marks: "join_layout", "join_gather" and, for sealed parts, "move_trailer".
- * Out of scope: parity blobs "DHP1" (a blob's rows span its whole input: the joined input wants a blob of its own, density_hip_parity_device); parts whose chunk
+ * A parity blob "DHP1" of A is kept current across an append or a replaced chunk by density_hip_parity_update_device (below), from the old and new bytes alone.
+ * Out of scope: joining parity blobs (a blob's rows span its whole input); parts whose chunk
  * sizes differ, and re-chunking; a ragged chunk anywhere but at the end; in-place joins, where the output overlaps a part. */
 #define DENSITY_HIP_JOIN_MAX_PARTS 64u
 typedef struct density_hip_join_part {
@@ -420,6 +421,43 @@ size_t density_hip_parity(const uint8_t* input, size_t input_size, size_t chunk_
 size_t density_hip_parity2_size(size_t input_size, size_t chunk_size, uint32_t n_groups);
 int density_hip_parity2_device(const void* d_input, size_t input_size, size_t chunk_size, uint32_t n_groups, void* d_parity, size_t parity_capacity, void* stream);
 size_t density_hip_parity2(const uint8_t* input, size_t input_size, size_t chunk_size, uint32_t n_groups, uint8_t* parity, size_t parity_capacity);
+/* Parity update: a blob kept current after its input was edited or appended to (a join that replaces chunk k or appends: above), without reading the input again.
+ * The blob is a linear code over the zero-padded input — P row g the XOR of its group's chunks, Q row g the XOR of 2^place · chunk — so an edit's effect on it is
+ * the same code applied to old ^ new, and only the rows of the chunks the edit covers are touched.
+ * The blob at d_parity (version 1 or 2, as its header says) is the blob of some input I; bytes [offset, offset + old_size) of I held `old`; they now hold `new`,
+ * new_size bytes long; the blob is updated in place.  Two shapes of edit are valid, and both may hold at once:
+ *   - same size: old_size == new_size and offset + old_size <= total_len — any byte offset and length, chunk-aligned or not;
+ *   - tail: offset + old_size == total_len — the input's tail from `offset` on is replaced by `new`, total_len becomes offset + new_size: append (old_size == 0, also
+ *     onto a ragged last chunk), truncation (new_size == 0), a tail of one length replaced by one of another.  The shorter of the two counts as zero-padded, which
+ *     is exact: the blob pads with zeros.
+ * The result is byte for byte what density_hip_parity_device / density_hip_parity2_device writes for the edited input with the blob's own chunk_size and n_groups;
+ * n_chunks and total_len of the header are rewritten on the device.  Rows no touched chunk belongs to are not written; inside touched rows only positions the
+ * edit covers can change.  Every 16-byte slot of a row is read, changed and written by one lane: no atomics, the same bytes every time.
+ * The call CANNOT CHECK `old`: with a wrong `old` the blob becomes a wrong blob — which, as ever, cannot pass wrong bytes: every rebuild is held against the
+ * container's trailer, and the chunk stays DENSITY_HIP_CHUNK_DAMAGED.
+ *   density_hip_parity_update_header: host arithmetic only, the one place the geometry rules live: *header_out (optional) = the header the blob has after the
+ *     edit.  DENSITY_HIP_OK, or DENSITY_HIP_ERR_ARGUMENT: a header that is not a blob's; an edit that is neither shape; offset + new_size overflowing or giving
+ *     more than 2^32 - 1 chunks; an edited input whose blob would not have this blob's geometry — fewer chunks than n_groups (shrinking to empty; growing an
+ *     empty blob, whose n_groups is 0) or round_up(min(chunk_size, new total_len), 16) != row_bytes (a one-chunk input shorter than chunk_size changing length
+ *     beyond its row): make a new blob —; version 2: a group growing beyond 255 members.
+ *   density_hip_parity_update_device: d_parity, d_old, d_new on the device at any byte alignment, none overlapping another; parity_header: optional HOST copy of the
+ *     blob's first 32 bytes (NULL: read back, one small synchronous copy); header_out: optional HOST pointer, filled by host arithmetic — it never makes the call
+ *     synchronise.  With parity_header the call is fully asynchronous on `stream`.
+ *   - DENSITY_HIP_ERR_ARGUMENT, nothing written, no device work — with parity_header decided before any device is acquired: NULL d_parity, NULL d_old with
+ *     old_size > 0, NULL d_new with new_size > 0, and whatever density_hip_parity_update_header refuses.
+ *   - DENSITY_HIP_ERR_FORMAT, nothing written: the header checks of density_hip_decode_device_recover — magic, version, n_groups outside 1 .. n_chunks, a row_bytes
+ *     that is not the formula's, a parity_size short of header plus rows (version 2: both kinds of rows), a version-2 header with groups of more than 255.
+ *   - old_size == new_size == 0: DENSITY_HIP_OK, nothing launched.
+ *   density_hip_parity_update: the host-pointer form, staged whole; returns the blob's size, 0 on failure with density_hip_last_error() set.
+ * Profiling mark: "parity_update".
+ * Out of scope: edits that insert or delete in the middle (every later chunk changes group and place); changing a blob's n_groups or chunk_size; slicing a blob. */
+int density_hip_parity_update_header(const density_hip_parity_header_t* header, uint64_t offset, size_t old_size, size_t new_size,
+                                     density_hip_parity_header_t* header_out);
+int density_hip_parity_update_device(void* d_parity, size_t parity_size, const density_hip_parity_header_t* parity_header,
+                                     uint64_t offset, const void* d_old, size_t old_size, const void* d_new, size_t new_size,
+                                     void* stream, density_hip_parity_header_t* header_out);
+size_t density_hip_parity_update(uint8_t* parity, size_t parity_size, uint64_t offset, const uint8_t* old_data, size_t old_size,
+                                 const uint8_t* new_data, size_t new_size);
 /* density_hip_decode_device_recover runs density_hip_decode_device_verdicts unchanged (the same kernels, the same workspace rules and sizes) and then, with the blob:
  *   - rebuild: for every group with exactly ONE damaged member k, chunk k's region of d_output is replaced by row g XOR the regions of the group's other
  *     members (the last chunk at its true length; no byte past total_len is written);
