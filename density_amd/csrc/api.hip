@@ -2,7 +2,8 @@
 // container's device-side drivers (encode in its three forms, decode, pack, unpage, slice, join) and the device-pointer / bookkeeping entry points.
 // (api_stream.hip: one reference stream, from device and from host pointers; api_host.hip: the host-pointer container calls.)  No CPU
 // codec lives here: every byte is produced by the gfx950 kernels, and every entry point fails (returns 0 / an error code) when no usable
-// HIP device is present.
+// HIP device is present.  Pack, unpage and slice are ONE driver: the packed form of a container is its chunk window [0, n_chunks), and run_windows — the
+// driver of the join — takes one part as it takes several.
 #include "api_internal.hpp"
 
 namespace density {
@@ -400,94 +401,6 @@ size_t parity_size_of(uint8_t version, size_t input_size, size_t chunk_size, uin
     return version == 2 && parity_group_members(ph) > kParityQMembers ? 0 : parity_bytes(ph);
 }
 
-// slotted container -> packed container (the wire form): header, size table and block index are copied, the payloads gathered
-int run_pack_container(DeviceCtx* c, const uint8_t* d_in, size_t container_size, const density_hip_header_t& h, uint8_t* d_out, size_t cap, uint8_t* ws,
-                       hipStream_t s, density_hip_header_t* header_out) {
-    const DecodePlan p = plan_decode(h.algo, h.n_chunks);
-    uint32_t* d_err = p.err(ws);
-    uint64_t *d_sizes = p.sizes(ws), *d_offsets = p.offsets(ws);
-    uint64_t* d_sizes64 = p.produced(ws);                                              // (the u64 sizes the layout kernel wants)
-    const bool with_index = h.flags & DENSITY_HIP_FLAG_BLOCK_INDEX;
-    const uint64_t pbase = payload_base(h.n_chunks, h.total_len, with_index);
-    // a sealed container: its trailer (not payload: the streams end in front of it) moves behind the packed streams, once the layout kernel has said where they end
-    const size_t trailer = header_trailer(h), body_len = h.container_len - trailer;
-    if (trailer) container_size = body_len;
-    if (cap < container_bound(h.algo, h.total_len, h.chunk_size) + (trailer ? seal_overhead(h.n_chunks) : 0)) {
-        set_error(trailer ? "output capacity below density_hip_container_bound() + density_hip_seal_overhead()" : "output capacity below density_hip_container_bound()");
-        return DENSITY_HIP_ERR_CAPACITY;
-    }
-    Profiler prof(c, s);
-    hipError_t e = hipMemsetAsync(d_err, 0, sizeof(uint32_t), s);
-    const uint64_t stride = (h.flags & DENSITY_HIP_FLAG_SLOTTED) ? slot_stride(h.algo, h.chunk_size) : 0;
-    // sizes (u64) and source offsets from the slotted container's table, then the packed layout into the output
-    if (e == hipSuccess) e = launch_layout_decode(d_in, container_size, h.n_chunks, pbase, d_sizes64, d_offsets, d_err, s, stride);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out + sizeof(h), d_in + sizeof(h), pbase - sizeof(h), hipMemcpyDeviceToDevice, s);   // size table + block index
-    density_hip_header_t out_h = h;
-    out_h.flags = h.flags & ~(DENSITY_HIP_FLAG_SLOTTED | DENSITY_HIP_FLAG_CHECKSUM);
-    out_h.container_len = 0;
-    if (e == hipSuccess) e = launch_layout_encode(d_sizes64, h.n_chunks, out_h, pbase, d_out, cap, d_sizes /* packed offsets */, d_err, s);
-    prof.mark("layout_encode");
-    if (e == hipSuccess) {
-        if (stride) e = launch_compact(d_in + pbase, stride, d_sizes64, d_sizes, h.n_chunks, d_out, d_err, s);
-        else if (body_len > cap || body_len < pbase) { set_error("output capacity below the container's length"); return DENSITY_HIP_ERR_CAPACITY; }
-        else e = hipMemcpyAsync(d_out + pbase, d_in + pbase, body_len - pbase, hipMemcpyDeviceToDevice, s);   // (already packed: its own bytes, no more)
-    }
-    prof.mark("compact");
-    if (trailer) {
-        if (e == hipSuccess) e = launch_move_trailer(d_in + body_len, d_out, cap, h.n_chunks, d_err, s);
-        prof.mark("move_trailer");
-    }
-    if (e != hipSuccess) { set_error("kernel launch (pack)", e); return DENSITY_HIP_ERR_RUNTIME; }
-    if (header_out) {
-        uint32_t h_err = 0;
-        e = read_back(s, d_err, &h_err, header_out, d_out, sizeof(*header_out));
-        if (e != hipSuccess) { set_error("pack (device)", e); return DENSITY_HIP_ERR_RUNTIME; }
-        if (h_err) { set_error("malformed slotted container"); return DENSITY_HIP_ERR_FORMAT; }
-    }
-    return DENSITY_HIP_OK;
-}
-
-// paged container -> packed container: size table and block index are copied, the directory is checked, the pages' used bytes gathered through it
-int run_unpage_container(DeviceCtx* c, const uint8_t* d_in, const density_hip_header_t& h, uint8_t* d_out, size_t cap, uint8_t* ws, hipStream_t s,
-                         density_hip_header_t* header_out) {
-    const DecodePlan p = plan_decode(h.algo, h.n_chunks);
-    uint32_t* d_err = p.err(ws);
-    uint64_t *d_offsets = p.sizes(ws) /* packed offsets */, *d_sizes64 = p.produced(ws);
-    const uint64_t pbase = paged_dir_base(h.n_chunks, h.total_len), pages_base = paged_pages_base(h.n_chunks, h.total_len, h.chunk_size);
-    const uint32_t ppc = paged_pages_per_chunk(h.chunk_size);
-    // a sealed container: the pages end in front of its trailer, which moves behind the packed streams once the layout kernel has said where they end
-    const size_t trailer = header_trailer(h), body_len = h.container_len - trailer;
-    if (cap < container_bound(h.algo, h.total_len, h.chunk_size) + (trailer ? seal_overhead(h.n_chunks) : 0)) {
-        set_error(trailer ? "output capacity below density_hip_container_bound() + density_hip_seal_overhead()" : "output capacity below density_hip_container_bound()");
-        return DENSITY_HIP_ERR_CAPACITY;
-    }
-    Profiler prof(c, s);
-    hipError_t e = hipMemsetAsync(d_err, 0, sizeof(uint32_t), s);
-    // sizes (u64) from the size table where the directory agrees with it, then the packed layout into the output
-    if (e == hipSuccess) e = launch_check_directory(d_in, h.n_chunks, h.chunk_size, h.total_len, pbase, ppc, (uint32_t)((body_len - pages_base) / kPageBytes), d_sizes64, d_err, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out + sizeof(h), d_in + sizeof(h), pbase - sizeof(h), hipMemcpyDeviceToDevice, s);   // size table + block index
-    density_hip_header_t out_h = h;
-    out_h.flags = h.flags & ~(DENSITY_HIP_FLAG_PAGED | DENSITY_HIP_FLAG_CHECKSUM);
-    out_h.container_len = 0;
-    if (e == hipSuccess) e = launch_layout_encode(d_sizes64, h.n_chunks, out_h, pbase, d_out, cap, d_offsets, d_err, s);
-    prof.mark("layout_encode");
-    if (e == hipSuccess) e = launch_unpage(d_in, h.n_chunks, pbase, pages_base, ppc, d_sizes64, d_offsets, d_out, d_err, s);
-    prof.mark("unpage");
-    if (trailer) {
-        if (e == hipSuccess) e = launch_move_trailer(d_in + body_len, d_out, cap, h.n_chunks, d_err, s);
-        prof.mark("move_trailer");
-    }
-    if (e != hipSuccess) { set_error("kernel launch (unpage)", e); return DENSITY_HIP_ERR_RUNTIME; }
-    if (header_out) {
-        uint32_t h_err = 0;
-        e = read_back(s, d_err, &h_err, header_out, d_out, sizeof(*header_out));
-        if (e != hipSuccess) { set_error("unpage (device)", e); return DENSITY_HIP_ERR_RUNTIME; }
-        if (h_err & 4u) { set_error("a page directory the call cannot follow"); return DENSITY_HIP_ERR_FORMAT; }
-        if (h_err) { set_error("container does not fit the output capacity"); return DENSITY_HIP_ERR_CAPACITY; }
-    }
-    return DENSITY_HIP_OK;
-}
-
 // ---- join: chunk windows of several containers as one packed container ----
 
 // what the host can say of a join before any byte moves: nullptr and *g, or why the part list is refused (include/density_hip.h: DENSITY_HIP_ERR_ARGUMENT)
@@ -533,14 +446,14 @@ int check_join_parts(const density_hip_join_part_t* parts, uint32_t n_parts) {
 // The parts' windows -> one packed container: everything the host can say of a part — where its size table, index bytes, trailer entries and (slotted) streams
 // lie — goes into the part table, which travels with the launches; where a packed part's window lies the layout kernel finds out and leaves on the device.
 // A paged part goes through the directory check and the unpage gather, handed offset pointers and its stretch of the run table.  What the caller brings
-// (WindowCall): the scratch in its own workspace, its profiling marks and its name in the messages.
+// (WindowCall): the scratch in its own workspace, and what WindowCaller says of it.
 struct WindowCall {
     uint32_t* err;
     uint64_t *lens, *src, *dst_off;       // a word per output chunk each
     uint64_t* run;                         // not null: one word, and a single packed part moves as the one run the layout kernel leaves there (the kernel
                                            // leaves 0 there for more than one part: then as with null, a run per chunk)
     uint64_t longest_run;                  // what no stream of a part that is not paged exceeds: sizes the gather's tiles per run
-    const char *layout_mark, *gather_mark, *name;
+    WindowCaller caller;
 };
 static int run_windows(DeviceCtx* c, const density_hip_join_part_t* parts, uint32_t n_parts, const JoinGeometry& g, uint8_t* d_out, size_t cap, const WindowCall& w,
                        hipStream_t s, density_hip_header_t* header_out) {
@@ -585,10 +498,13 @@ static int run_windows(DeviceCtx* c, const density_hip_join_part_t* parts, uint3
         ++live;
     }
     if (e == hipSuccess) e = launch_window_layout(src, live, (uint32_t)g.algo, g.chunk_size, d_out, cap, out_h, out_base, d_lens, d_src, d_dst_off, w.run, d_err, s);
-    prof.mark(w.layout_mark);
+    prof.mark(w.caller.layout_mark);
     if (e == hipSuccess) {
-        // one packed part of a caller that asked for it: ONE run, its streams lie as the output wants them, gaps included; else a run per chunk (none of a paged part's)
+        // one packed part of a caller that asked for it: ONE run, its streams lie as the output wants them, gaps included; one slotted part of a caller that asked
+        // for that: the encoder's gather over its slots; else a run per chunk (none of a paged part's)
         if (w.run && live == 1 && src.p[0].slot_stride == 0) e = launch_run_gather(d_src, w.run, d_dst_off, 1, src.p[0].limit - src.p[0].src_base, d_out, d_err, s);
+        else if (w.caller.compact_slots && live == 1 && src.p[0].slot_stride != kJoinPaged)
+            e = launch_compact(src.p[0].in + src.p[0].src_base + src.p[0].first * src.p[0].slot_stride, src.p[0].slot_stride, d_lens, d_dst_off, (uint32_t)g.n_chunks, d_out, d_err, s);
         else if (any_unpaged) e = launch_run_gather(d_src, d_lens, d_dst_off, (uint32_t)g.n_chunks, w.longest_run, d_out, d_err, s);
     }
     K = 0;
@@ -601,12 +517,12 @@ static int run_windows(DeviceCtx* c, const density_hip_join_part_t* parts, uint3
                               paged_pages_base(h.n_chunks, h.total_len, h.chunk_size), ppc, d_lens + K, d_dst_off + K, d_out, d_err, s);
         K += q.chunk_count;
     }
-    prof.mark(w.gather_mark);
+    prof.mark(w.caller.gather_mark);
     if (sealed) {
         if (e == hipSuccess) e = launch_place_trailer(trailers, live, d_out, cap, (uint32_t)g.n_chunks, d_err, s);
         prof.mark("move_trailer");
     }
-    const auto named = [&w](const char* front, const char* back) { return std::string(front) + w.name + back; };   // (a refusal's message: nothing is built where none is raised)
+    const auto named = [&w](const char* front, const char* back) { return std::string(front) + w.caller.name + back; };   // (a refusal's message: nothing is built where none is raised)
     if (e != hipSuccess) { set_error(named("kernel launch (", ")").c_str(), e); return DENSITY_HIP_ERR_RUNTIME; }
     if (header_out) {
         uint32_t h_err = 0;
@@ -618,20 +534,23 @@ static int run_windows(DeviceCtx* c, const density_hip_join_part_t* parts, uint3
     return DENSITY_HIP_OK;
 }
 
-// a slice is a join of one part; its tables lie in plan_decode's arrays of the SOURCE (density_hip_decode_workspace_size), its packed window moves as one run
+// A slice is a join of one part; its tables lie in plan_decode's arrays of the SOURCE (density_hip_decode_workspace_size), its packed window moves as one run.
+// Pack and unpage are the slice [0, h.n_chunks) under marks and a name of their own (an empty container: a part that is skipped, and the front matter alone;
+// it has no trailer, so it packs as an unsealed one).
 int run_slice_container(DeviceCtx* c, const uint8_t* d_in, const density_hip_header_t& h, uint32_t first, uint32_t count, uint8_t* d_out, size_t cap, uint8_t* ws,
-                        hipStream_t s, density_hip_header_t* header_out) {
+                        hipStream_t s, density_hip_header_t* header_out, const WindowCaller& caller) {
     const DecodePlan p = plan_decode(h.algo, h.n_chunks);
     const density_hip_join_part_t part{d_in, (size_t)h.container_len, &h, first, count};
-    const JoinGeometry g{h.algo, h.chunk_size, (uint32_t)h.flags & (DENSITY_HIP_FLAG_BLOCK_INDEX | DENSITY_HIP_FLAG_CHECKSUM), 1, count, slice_len(h, first, count)};
-    const WindowCall w{p.err(ws), p.produced(ws), p.offsets(ws), p.sizes(ws), p.offsets(ws) + h.n_chunks, (h.flags & DENSITY_HIP_FLAG_SLOTTED) ? slot_stride(h.algo, h.chunk_size) : safe_size(h.algo, h.chunk_size), "slice_layout", "slice_gather", "slice"};
+    const uint32_t flags = (h.flags & DENSITY_HIP_FLAG_BLOCK_INDEX) | (header_trailer(h) ? DENSITY_HIP_FLAG_CHECKSUM : 0);
+    const JoinGeometry g{h.algo, h.chunk_size, flags, 1, count, slice_len(h, first, count)};
+    const WindowCall w{p.err(ws), p.produced(ws), p.offsets(ws), p.sizes(ws), p.offsets(ws) + h.n_chunks, (h.flags & DENSITY_HIP_FLAG_SLOTTED) ? slot_stride(h.algo, h.chunk_size) : safe_size(h.algo, h.chunk_size), caller};
     return run_windows(c, &part, 1, g, d_out, cap, w, s, header_out);
 }
 
 int run_join_container(DeviceCtx* c, const density_hip_join_part_t* parts, uint32_t n_parts, const JoinGeometry& g, uint8_t* d_out, size_t cap, uint8_t* ws,
                        hipStream_t s, density_hip_header_t* header_out) {
     const JoinPlan p = plan_join(g.n_chunks);
-    const WindowCall w{p.err(ws), p.lens(ws), p.src(ws), p.dst_off(ws), nullptr, safe_size(g.algo, g.chunk_size), "join_layout", "join_gather", "join"};
+    const WindowCall w{p.err(ws), p.lens(ws), p.src(ws), p.dst_off(ws), nullptr, safe_size(g.algo, g.chunk_size), {"join_layout", "join_gather", "join", false}};
     return run_windows(c, parts, n_parts, g, d_out, cap, w, s, header_out);
 }
 
@@ -676,17 +595,55 @@ int encode_device(Form form, int algo, const void* d_input, size_t input_size, v
     if (const int rc = resolve_workspace(c, d_workspace, workspace_size, need, need, &ws)) return rc;
     return run_encode_container(c, algo, (const uint8_t*)d_input, input_size, (uint8_t*)d_output, output_capacity, chunk_size, ws, stream ? (hipStream_t)stream : c->stream, header_out, form);
 }
-// the header of a container on the device: the caller's copy, or read back on s — ordered behind whatever produced the container on the caller's
-// stream (streams here are non-blocking: a plain hipMemcpy is not) — and checked against the container's size
+// the header of an object on the device: the caller's copy, or read back on s — ordered behind whatever produced the object on the caller's
+// stream (streams here are non-blocking: a plain hipMemcpy is not).  Not judged here.
+template <typename Header>
+int fetch_header(const Header* header, const void* d_object, hipStream_t s, Header* h, const char* what) {
+    if (header) { *h = *header; return DENSITY_HIP_OK; }
+    hipError_t e = hipMemcpyAsync(h, d_object, sizeof(*h), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { set_error(what, e); return DENSITY_HIP_ERR_RUNTIME; }
+    return DENSITY_HIP_OK;
+}
+// a container's header, checked against the container's size
 int container_header(const density_hip_header_t* header, const void* d_container, size_t container_size, hipStream_t s, density_hip_header_t* h) {
-    if (header) *h = *header;
-    else {
-        hipError_t e = hipMemcpyAsync(h, d_container, sizeof(*h), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { set_error("header read-back", e); return DENSITY_HIP_ERR_RUNTIME; }
-    }
+    if (const int rc = fetch_header(header, d_container, s, h, "header read-back")) return rc;
     if (check_header(*h, container_size) != DENSITY_HIP_OK) { set_error("bad container header"); return DENSITY_HIP_ERR_FORMAT; }
     return DENSITY_HIP_OK;
+}
+// a parity blob's header (at least sizeof(*ph) bytes of the blob are there); check_parity_header / check_parity_update judge it
+int parity_header(const density_hip_parity_header_t* header, const void* d_parity, hipStream_t s, density_hip_parity_header_t* ph) {
+    return fetch_header(header, d_parity, s, ph, "parity header read-back");
+}
+// The opening of the calls that repack ONE container (density_hip_pack_device, _unpage_device, _slice_device): the arguments all of them refuse, the context
+// — locked while the Repack lives —, the stream and the container's header as fetch_header gives it.  What a call asks of the header, in which order and under
+// which code, stands in the call; then the workspace (plan_decode's arrays of the source) and the driver, run_slice_container.
+struct Repack {
+    DeviceCtx* c = nullptr;
+    std::unique_lock<std::mutex> lk;
+    hipStream_t s = nullptr;
+    density_hip_header_t h;
+    uint8_t* ws = nullptr;
+};
+int open_repack(const void* d_container, size_t container_size, const density_hip_header_t* header, const void* d_output, void* stream, Repack* r) {
+    g_last_error.clear();
+    if (!d_container || container_size < sizeof(density_hip_header_t) || !d_output) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
+    r->c = acquire_ctx();
+    if (!r->c) return DENSITY_HIP_ERR_RUNTIME;
+    r->lk = std::unique_lock<std::mutex>(r->c->mu);
+    r->s = stream ? (hipStream_t)stream : r->c->stream;
+    return fetch_header(header, d_container, r->s, &r->h, "header read-back");
+}
+int repack_workspace(Repack* r, void* d_workspace, size_t workspace_size) {
+    const size_t need = plan_decode(r->h.algo, r->h.n_chunks).total;
+    return resolve_workspace(r->c, d_workspace, workspace_size, need, need, &r->ws);
+}
+// what pack and unpage ask of the output: the packed bound of the whole container, and the seal's share where a trailer comes along
+int whole_capacity(const density_hip_header_t& h, size_t cap) {
+    const bool trailer = header_trailer(h) != 0;
+    if (cap >= container_bound(h.algo, h.total_len, h.chunk_size) + (trailer ? seal_overhead(h.n_chunks) : 0)) return DENSITY_HIP_OK;
+    set_error(trailer ? "output capacity below density_hip_container_bound() + density_hip_seal_overhead()" : "output capacity below density_hip_container_bound()");
+    return DENSITY_HIP_ERR_CAPACITY;
 }
 // density_hip_parity_device and density_hip_parity2_device: they differ in the blob's version
 int parity_device(uint8_t version, const void* d_input, size_t input_size, size_t chunk_size, uint32_t n_groups, void* d_parity, size_t parity_capacity, void* stream) {
@@ -757,37 +714,25 @@ size_t density_hip_container_bound_slotted(int algo, size_t input_size, size_t c
 
 int density_hip_pack_device(const void* d_container, size_t container_size, const density_hip_header_t* header, void* d_output,
                             size_t output_capacity, void* d_workspace, size_t workspace_size, void* stream, density_hip_header_t* header_out) {
-    g_last_error.clear();
-    if (!d_container || container_size < sizeof(density_hip_header_t) || !d_output) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
-    DeviceCtx* c = acquire_ctx();
-    if (!c) return DENSITY_HIP_ERR_RUNTIME;
-    std::lock_guard<std::mutex> lk(c->mu);
-    density_hip_header_t h;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (const int rc = container_header(header, d_container, container_size, s, &h)) return rc;
+    Repack r;
+    if (const int rc = open_repack(d_container, container_size, header, d_output, stream, &r)) return rc;
+    if (check_header(r.h, container_size) != DENSITY_HIP_OK) { set_error("bad container header"); return DENSITY_HIP_ERR_FORMAT; }
     // a PAGED container is wire-ready as it stands, and its streams are not where the packed / slotted arithmetic looks for them
-    if (h.flags & DENSITY_HIP_FLAG_PAGED) { set_error("density_hip_pack_device: a paged container is not packed (it is wire-ready; decode it or read its pages)"); return DENSITY_HIP_ERR_UNSUPPORTED; }
-    const size_t need = plan_decode(h.algo, h.n_chunks).total;
-    uint8_t* ws = nullptr;
-    if (const int rc = resolve_workspace(c, d_workspace, workspace_size, need, need, &ws)) return rc;
-    return run_pack_container(c, (const uint8_t*)d_container, container_size, h, (uint8_t*)d_output, output_capacity, ws, s, header_out);
+    if (r.h.flags & DENSITY_HIP_FLAG_PAGED) { set_error("density_hip_pack_device: a paged container is not packed (it is wire-ready; decode it or read its pages)"); return DENSITY_HIP_ERR_UNSUPPORTED; }
+    if (const int rc = repack_workspace(&r, d_workspace, workspace_size)) return rc;
+    if (const int rc = whole_capacity(r.h, output_capacity)) return rc;
+    return run_slice_container(r.c, (const uint8_t*)d_container, r.h, 0, r.h.n_chunks, (uint8_t*)d_output, output_capacity, r.ws, r.s, header_out, {"layout_encode", "compact", "pack", true});
 }
 
 int density_hip_unpage_device(const void* d_container, size_t container_size, const density_hip_header_t* header, void* d_output,
                               size_t output_capacity, void* d_workspace, size_t workspace_size, void* stream, density_hip_header_t* header_out) {
-    g_last_error.clear();
-    if (!d_container || container_size < sizeof(density_hip_header_t) || !d_output) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
-    DeviceCtx* c = acquire_ctx();
-    if (!c) return DENSITY_HIP_ERR_RUNTIME;
-    std::lock_guard<std::mutex> lk(c->mu);
-    density_hip_header_t h;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (const int rc = container_header(header, d_container, container_size, s, &h)) return rc;
-    if (!(h.flags & DENSITY_HIP_FLAG_PAGED)) { set_error("density_hip_unpage_device: not a paged container (density_hip_pack_device takes the packed and slotted forms)"); return DENSITY_HIP_ERR_ARGUMENT; }
-    const size_t need = plan_decode(h.algo, h.n_chunks).total;
-    uint8_t* ws = nullptr;
-    if (const int rc = resolve_workspace(c, d_workspace, workspace_size, need, need, &ws)) return rc;
-    return run_unpage_container(c, (const uint8_t*)d_container, h, (uint8_t*)d_output, output_capacity, ws, s, header_out);
+    Repack r;
+    if (const int rc = open_repack(d_container, container_size, header, d_output, stream, &r)) return rc;
+    if (check_header(r.h, container_size) != DENSITY_HIP_OK) { set_error("bad container header"); return DENSITY_HIP_ERR_FORMAT; }
+    if (!(r.h.flags & DENSITY_HIP_FLAG_PAGED)) { set_error("density_hip_unpage_device: not a paged container (density_hip_pack_device takes the packed and slotted forms)"); return DENSITY_HIP_ERR_ARGUMENT; }
+    if (const int rc = repack_workspace(&r, d_workspace, workspace_size)) return rc;
+    if (const int rc = whole_capacity(r.h, output_capacity)) return rc;
+    return run_slice_container(r.c, (const uint8_t*)d_container, r.h, 0, r.h.n_chunks, (uint8_t*)d_output, output_capacity, r.ws, r.s, header_out, {"layout_encode", "unpage", "unpage", false});
 }
 
 int density_hip_chunk_range(const density_hip_header_t* header, uint64_t offset, uint64_t length, uint32_t* first_chunk, uint32_t* chunk_count, uint64_t* skip) {
@@ -806,27 +751,15 @@ size_t density_hip_slice_bound(const density_hip_header_t* header, uint32_t firs
 
 int density_hip_slice_device(const void* d_container, size_t container_size, const density_hip_header_t* header, uint32_t first_chunk, uint32_t chunk_count, void* d_output,
                              size_t output_capacity, void* d_workspace, size_t workspace_size, void* stream, density_hip_header_t* header_out) {
-    g_last_error.clear();
-    if (!d_container || container_size < sizeof(density_hip_header_t) || !d_output || chunk_count == 0) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
-    DeviceCtx* c = acquire_ctx();
-    if (!c) return DENSITY_HIP_ERR_RUNTIME;
-    std::lock_guard<std::mutex> lk(c->mu);
-    density_hip_header_t h;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (header) h = *header;
-    else {
-        hipError_t e = hipMemcpyAsync(&h, d_container, sizeof(h), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { set_error("header read-back", e); return DENSITY_HIP_ERR_RUNTIME; }
-    }
-    if (!header_is_containers(h)) { set_error("slice: not a container's header"); return DENSITY_HIP_ERR_ARGUMENT; }
-    if ((uint64_t)first_chunk + chunk_count > h.n_chunks) { set_error("slice: the window is not inside the container's chunks"); return DENSITY_HIP_ERR_ARGUMENT; }
-    if (output_capacity < slice_bound(h, first_chunk, chunk_count)) { set_error("output capacity below density_hip_slice_bound()"); return DENSITY_HIP_ERR_CAPACITY; }
-    if (check_header(h, container_size) != DENSITY_HIP_OK) { set_error("bad container header (its length, or its trailer's, against container_size)"); return DENSITY_HIP_ERR_FORMAT; }
-    const size_t need = plan_decode(h.algo, h.n_chunks).total;
-    uint8_t* ws = nullptr;
-    if (const int rc = resolve_workspace(c, d_workspace, workspace_size, need, need, &ws)) return rc;
-    return run_slice_container(c, (const uint8_t*)d_container, h, first_chunk, chunk_count, (uint8_t*)d_output, output_capacity, ws, s, header_out);
+    if (chunk_count == 0) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
+    Repack r;
+    if (const int rc = open_repack(d_container, container_size, header, d_output, stream, &r)) return rc;
+    if (!header_is_containers(r.h)) { set_error("slice: not a container's header"); return DENSITY_HIP_ERR_ARGUMENT; }
+    if ((uint64_t)first_chunk + chunk_count > r.h.n_chunks) { set_error("slice: the window is not inside the container's chunks"); return DENSITY_HIP_ERR_ARGUMENT; }
+    if (output_capacity < slice_bound(r.h, first_chunk, chunk_count)) { set_error("output capacity below density_hip_slice_bound()"); return DENSITY_HIP_ERR_CAPACITY; }
+    if (check_header(r.h, container_size) != DENSITY_HIP_OK) { set_error("bad container header (its length, or its trailer's, against container_size)"); return DENSITY_HIP_ERR_FORMAT; }
+    if (const int rc = repack_workspace(&r, d_workspace, workspace_size)) return rc;
+    return run_slice_container(r.c, (const uint8_t*)d_container, r.h, first_chunk, chunk_count, (uint8_t*)d_output, output_capacity, r.ws, r.s, header_out);
 }
 
 size_t density_hip_join_bound(const density_hip_join_part_t* parts, uint32_t n_parts) {
@@ -916,12 +849,7 @@ int density_hip_decode_device_recover(const void* d_container, size_t container_
     if (!d_verdicts && h.n_chunks) { set_error("bad argument"); return DENSITY_HIP_ERR_ARGUMENT; }
     if (parity_size < sizeof(density_hip_parity_header_t)) { set_error("parity blob shorter than its header"); return DENSITY_HIP_ERR_FORMAT; }
     density_hip_parity_header_t ph;
-    if (parity_header) ph = *parity_header;
-    else {
-        hipError_t e = hipMemcpyAsync(&ph, d_parity, sizeof(ph), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { set_error("parity header read-back", e); return DENSITY_HIP_ERR_RUNTIME; }
-    }
+    if (const int rc = api::parity_header(parity_header, d_parity, s, &ph)) return rc;
     if (const int rc = check_parity_header(ph, h, parity_size)) return rc;
     const DecodePlan dp = plan_decode(h.algo, h.n_chunks, h.chunk_size);      // (the workspace rules of density_hip_decode_device)
     uint8_t* ws = nullptr;
@@ -977,9 +905,7 @@ int density_hip_parity_update_device(void* d_parity, size_t parity_size, const d
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     if (!parity_header) {
         density_hip_parity_header_t ph;
-        hipError_t e = hipMemcpyAsync(&ph, d_parity, sizeof(ph), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { set_error("parity header read-back", e); return DENSITY_HIP_ERR_RUNTIME; }
+        if (const int rc = api::parity_header(nullptr, d_parity, s, &ph)) return rc;
         if (const int rc = check_parity_update(ph, parity_size, offset, old_size, new_size, &after)) return rc;
         if (header_out) *header_out = after;
         if (!old_size && !new_size) return DENSITY_HIP_OK;

@@ -1,5 +1,5 @@
 // api_internal.hpp — what the three units of the C ABI share.  api.hip: per-device context, workspace plans, the container's device-side
-// drivers, the device-pointer and bookkeeping entry points.  api_stream.hip: ONE reference stream — the reference's nine symbols and their
+// drivers (pack, unpage and slice are one: run_slice_container), the device-pointer and bookkeeping entry points.  api_stream.hip: ONE reference stream — the reference's nine symbols and their
 // device-pointer forms, long Chameleon streams in parallel segments, staged or pipelined from host pointers.  api_host.hip: the host-pointer
 // container calls, staged or pipelined in slices.  Here: geometry of the formats, the context, the kernel-variant bits, the workspace plans with
 // their typed views, and the steps every driver repeats (workspace resolution, read-back, drain, slice arithmetic).  Internal to libdensity_hip.so.
@@ -388,9 +388,14 @@ size_t parity_size_of(uint8_t version, size_t input_size, size_t chunk_size, uin
 // the seal of the container just encoded for d_in (`ws`: plan_seal(n).total bytes); `header`: the caller's copy of its header, or nullptr
 int run_seal_container(DeviceCtx* c, const uint8_t* d_in, size_t n, uint8_t* d_out, size_t cap, const density_hip_header_t* header, uint8_t* ws, hipStream_t s,
                        density_hip_header_t* header_out);
-// chunks [first, first + count) of the container at d_in (header h: checked, the window inside it, cap >= slice_bound()) as a packed container at d_out
+// chunks [first, first + count) of the container at d_in (header h: checked, the window inside it, cap >= slice_bound()) as a packed container at d_out.
+// The one driver of density_hip_slice_device, density_hip_pack_device and density_hip_unpage_device: the last two are the window [0, h.n_chunks) — of no
+// chunks for an empty container, cap >= container_bound() — and differ in what they ask of the header and in what WindowCaller holds: the two profiling
+// marks, the call's name in the messages, and whether a SLOTTED source's streams are gathered by compact_kernel, the packed encode's gather, instead of
+// run_gather_kernel.  The pack asks for that: on a whole slotted container of 1 GiB the run gather measured 5 % behind it (profiles/repack_rate.txt).
+struct WindowCaller { const char *layout_mark, *gather_mark, *name; bool compact_slots; };
 int run_slice_container(DeviceCtx* c, const uint8_t* d_in, const density_hip_header_t& h, uint32_t first, uint32_t count, uint8_t* d_out, size_t cap, uint8_t* ws,
-                        hipStream_t s, density_hip_header_t* header_out);
+                        hipStream_t s, density_hip_header_t* header_out, const WindowCaller& caller = {"slice_layout", "slice_gather", "slice", false});
 // a join (density_hip_join_device): what its part list comes to — algorithm, chunk size and the flags the parts share, the output's chunks and input bytes, the
 // parts that are not skipped — or why it is refused; the capacity it asks for; every live part's header against its container_size (DENSITY_HIP_ERR_FORMAT)
 struct JoinGeometry { int algo; uint32_t chunk_size, flags, live; uint64_t n_chunks, total_len; };

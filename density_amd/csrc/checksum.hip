@@ -207,10 +207,4 @@ hipError_t launch_place_trailer(const TrailerRuns& runs, uint32_t n_parts, uint8
     return hipGetLastError();
 }
 
-hipError_t launch_move_trailer(const uint8_t* d_trailer, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err, hipStream_t stream) {
-    TrailerRuns one{};
-    one.p[0] = TrailerRun{d_trailer, 0, n_chunks};
-    return launch_place_trailer(one, 1, d_container, capacity, n_chunks, d_err, stream);
-}
-
 }  // namespace density

@@ -167,12 +167,12 @@ hipError_t launch_layout_encode_batch(const uint64_t* d_sizes, uint32_t first, u
 // Decode side: reads the u32 size table of a container, produces u64 sizes + offsets, validates against container_size.
 hipError_t launch_layout_decode(const uint8_t* d_container, uint64_t container_size, uint32_t n_chunks, uint64_t payload_base,
                                 uint64_t* d_sizes, uint64_t* d_offsets, uint32_t* d_err, hipStream_t stream, uint64_t slot_stride = 0);
-// Gathers chunk streams from their worst-case slots into the packed container.
+// Gathers chunk streams from their worst-case slots into the packed container (the packed encode; density_hip_pack_device of a slotted container).
 hipError_t launch_compact(const uint8_t* d_slots, uint64_t slot_stride, const uint64_t* d_sizes, const uint64_t* d_offsets,
                           uint32_t n_chunks, uint8_t* d_container, const uint32_t* d_err, hipStream_t stream, bool more_follow = false);
 // (`more_follow`: the launch gathers one batch of a container and further streams follow its last one — the alignment gap behind that stream
 // is then zero-filled like the gaps between the launch's own streams, so that a batched gather writes the same bytes as a single one)
-// PAGED container -> packed container (density_hip_unpage_device).  The check: a wave per chunk holds the chunk's directory against the size table and the
+// PAGED container -> packed container (density_hip_unpage_device; a paged part of a slice or join).  The check: a wave per chunk holds the chunk's directory against the size table and the
 // container (n_pages: the pages it holds); d_sizes[c] = the stream's length, or 0 with bit 4 of *d_err where the gather may not follow the directory.
 hipError_t launch_check_directory(const uint8_t* d_container, uint32_t n_chunks, uint64_t chunk_bytes, uint64_t total_len, uint64_t dir_base,
                                   uint32_t pages_per_chunk, uint32_t n_pages, uint64_t* d_sizes, uint32_t* d_err, hipStream_t stream);
@@ -180,7 +180,8 @@ hipError_t launch_check_directory(const uint8_t* d_container, uint32_t n_chunks,
 // gaps between the streams included; nothing where *d_err is set.
 hipError_t launch_unpage(const uint8_t* d_container, uint32_t n_chunks, uint64_t dir_base, uint64_t pages_base, uint32_t pages_per_chunk,
                          const uint64_t* d_sizes, const uint64_t* d_offsets, uint8_t* d_out, const uint32_t* d_err, hipStream_t stream);
-// Chunk windows [first, first + count) of one or several containers -> one packed container (density_hip_slice_device: one part; density_hip_join_device).
+// Chunk windows [first, first + count) of one or several containers -> one packed container (density_hip_join_device; one part: density_hip_slice_device, and
+// as the window [0, n_chunks) density_hip_pack_device and density_hip_unpage_device — api.hip has one driver for the four).
 // The part table travels as a kernel argument (3 KiB of the 4 KiB there are: it is read when the launch is made, so the caller's table may go at once): per
 // part where the container lies, where its streams end (`limit`), its total_len and payload base (paged: unused), how its streams lie (slot_stride: 0
 // packed — the size table is scanned from chunk 0 for the window's place —, kJoinPaged paged, else slotted), the window.
@@ -224,13 +225,11 @@ hipError_t launch_blank_chunks(uint8_t* d_out, uint64_t size, uint32_t chunk, ui
 hipError_t launch_seal(const uint8_t* d_in, uint64_t input_size, uint8_t* d_container, uint64_t capacity, uint32_t* d_geom, uint32_t* d_acc, uint32_t* d_err,
                        hipStream_t stream);
 // A trailer of n_chunks words to its place behind the packed container the layout and gather kernels have just written, gathered from n_parts runs: run p is
-// `count` words at `src`, placed from entry `entry` on; the runs cover entries 0 .. n_chunks - 1 once (a join: a run per part; a slice: one run)
+// `count` words at `src`, placed from entry `entry` on; the runs cover entries 0 .. n_chunks - 1 once (a join: a run per part; a slice, a pack, an unpage: one run)
 struct TrailerRun { const uint8_t* src; uint32_t entry, count; };
 struct TrailerRuns { TrailerRun p[kJoinMaxParts]; };
 hipError_t launch_place_trailer(const TrailerRuns& runs, uint32_t n_parts, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err,
                                 hipStream_t stream);
-// ... as one run, the n_chunks words at d_trailer (density_hip_pack_device, density_hip_unpage_device)
-hipError_t launch_move_trailer(const uint8_t* d_trailer, uint8_t* d_container, uint64_t capacity, uint32_t n_chunks, uint32_t* d_err, hipStream_t stream);
 
 // ---- parity.hip (recovery records: the parity blob "DHP1" of include/density_hip.h, and the rebuild behind a verdict decode) ----
 // The blob of d_data (hdr.total_len bytes, any alignment) into d_blob (any alignment): hdr itself, then hdr.n_groups rows of hdr.row_bytes bytes — with

@@ -214,12 +214,19 @@ size_t density_hip_paged_pages_per_chunk(size_t chunk_size);
 int density_hip_encode_device_paged(int algo, const void* d_input, size_t input_size, void* d_output, size_t output_capacity,
                                     size_t chunk_size, void* d_workspace, size_t workspace_size, void* stream,
                                     density_hip_header_t* header_out);
-/* Slotted (or packed) container -> packed container: byte for byte what density_hip_encode_device() writes for the same input.  Workspace as for
- * decode.  With header_out == NULL the call is asynchronous and reports nothing about the container it was given (a size table that does not
- * fit its slots or the container leaves the output unwritten): pass header_out to have it validated. */
+/* Slotted (or packed) container, sealed or not -> packed container: byte for byte what density_hip_encode_device() (+ density_hip_seal_device()) writes for
+ * the same input.  The call is density_hip_slice_device() of the window [0, n_chunks) — one driver runs pack, unpage and slice —, so what that call says of
+ * alignment, of the faults found on the device (a size-table entry above {algo}_safe_encode_buffer_size of its chunk's input or above its slot, streams that
+ * run past the container: DENSITY_HIP_ERR_FORMAT, no payload byte written) and of the gaps (zeros, but a packed source moves as one run with the gaps between
+ * its streams as they stand) holds here.  Its own: `output_capacity` at least density_hip_container_bound(), plus density_hip_seal_overhead() for a sealed
+ * input (less: DENSITY_HIP_ERR_CAPACITY at once, nothing written); a PAGED container is DENSITY_HIP_ERR_UNSUPPORTED (density_hip_unpage_device is for those);
+ * a container of no chunks is taken.  Workspace as for decode.  With header_out == NULL the call is asynchronous and reports nothing about the container it was
+ * given (a refused size table leaves the payloads unwritten): pass header_out to have it validated.
+ * Profiling marks: "layout_encode", "compact" and, for a sealed source, "move_trailer". */
 int density_hip_pack_device(const void* d_container, size_t container_size, const density_hip_header_t* header, void* d_output,
                             size_t output_capacity, void* d_workspace, size_t workspace_size, void* stream, density_hip_header_t* header_out);
-/* Paged container -> packed container: the gather density_hip_pack_device does for the slotted form, over the page directory.  The input is a PAGED
+/* Paged container -> packed container: what density_hip_pack_device does for the slotted form, over the page directory — density_hip_slice_device() of the
+ * window [0, n_chunks) of a paged source, through the same driver (profiling marks: "layout_encode", "unpage" and, sealed, "move_trailer").  The input is a PAGED
  * container, sealed or not; the output is the packed container of the same chunks with DENSITY_HIP_FLAG_BLOCK_INDEX (and DENSITY_HIP_FLAG_CHECKSUM if the
  * input was sealed): byte for byte what density_hip_encode_device() (+ density_hip_seal_device()) writes for the same input — header, size table, block
  * index, the 16-byte-aligned payloads with zero gaps, container_len, the trailer behind round_up(E, 16) — whatever order the pages were taken in.  The page

@@ -2,7 +2,8 @@
 4 MiB Chameleon chunks — packed, and the first also paged, the second also slotted.  Measured, in ONE process and alternating: the join of the two packed
 halves, the join of the paged and the slotted half, the replacement of a single chunk of the whole packed container (container.replace_chunks_device), and
 beside them density_hip_slice_device of the whole packed container's window [0, n) (the same bytes through the one-source kernels), density_hip_pack_device of
-each slotted-or-packed half and density_hip_unpage_device of the paged half (the same halves through the calls that move a container whole).  Everything warmed
+each slotted-or-packed half and density_hip_unpage_device of the paged half (the same halves through the calls that move a container whole: since pack,
+unpage and slice share the join's driver these run the join's layout kernel too and, but for the slotted pack's compact_kernel, its gathers).  Everything warmed
 up, 20 timed repetitions each with HIP events; min / median / max, bytes written, and the ratios of the medians.  A report, not a gate.
 
 Three steps, each a process of its own under its own `timeout`, the first failure ends the run: "check" (the joins' bytes against density_hip_encode_device of

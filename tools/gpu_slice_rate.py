@@ -1,5 +1,7 @@
-"""What a slice costs (density_hip_slice_device) against the calls that move the same container whole: density_hip_pack_device on the PACKED container (one
-device copy of the payload area) and density_hip_unpage_device on the PAGED one (unpage_kernel over the whole directory).  One process, same box: 1 GiB of
+"""What a slice costs (density_hip_slice_device) against the calls that move the same container whole: density_hip_pack_device on the PACKED container and
+density_hip_unpage_device on the PAGED one.  Since pack, unpage and slice share one driver these are the SAME kernels as the slice of the window [0, n) — the
+window layout, then one run of run_gather_kernel (packed) or unpage_kernel over the whole directory (paged) — under other marks, so the whole-window ratios
+say what the box's repeatability is, no more (profiles/slice_rate.txt is from before: the pack was a device copy then).  One process, same box: 1 GiB of
 rep-text in automatic 4 MiB chunks; per form the whole window [0, n) — the same bytes as the yardstick — and the middle half [n/4, n/4 + n/2); everything
 warmed up, 20 timed repetitions each with HIP events, the paths alternating; min / median / max of each, the ratio of the medians full window / yardstick,
 and the marks of the library's own profiling.  A report, not a gate.

@@ -1,5 +1,6 @@
 """What bringing a PAGED container to the packed wire form costs (density_hip_unpage_device) against the yardstick that moves the same bytes: density_hip_pack_device
-on the SLOTTED container of the same input (compact_kernel: E bytes read, E bytes written).  One process, same box: 1 GiB of rep-text in automatic 4 MiB
+on the SLOTTED container of the same input (compact_kernel: E bytes read, E bytes written).  Pack, unpage and slice share one driver: the two calls differ
+in their gather kernel alone, layout and trailer are the same kernels.  One process, same box: 1 GiB of rep-text in automatic 4 MiB
 chunks, both paths warmed up, 20 timed repetitions each with HIP events, alternating the two; min / median / max of each and the ratio of the medians.
 python tools/gpu_unpage_rate.py [out=profiles/unpage_rate.txt]"""
 import os, statistics, sys
